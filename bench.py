@@ -6,7 +6,7 @@ plus GSWorld's uint8 frame conversion, on a synthetic xarm6_align-like scene (1,
 sensor camera `right_cam`; BASELINE.json configs[1]).  Inputs are resident in HBM before the timed
 region.  N > 1: one independent scene per GPU (configs[3]); finished uint8 frames are gathered with RCCL.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 from __future__ import annotations
@@ -44,10 +44,12 @@ def parse():
     ap.add_argument("--render-bpc", type=int, default=0, help="persistent compositing workgroups per CU (0 = library default)")
     ap.add_argument("--no-layout", action="store_true",
                     help="render the model in the order it was given, without block culling (gsworld_amd/layout.py)")
-    ap.add_argument("--blocks", type=int, default=25,
-                    help="timed blocks of --steps steps each (at least this many, and until --min-seconds are timed); "
-                         "value = their median")
-    ap.add_argument("--min-seconds", type=float, default=0.3)
+    ap.add_argument("--blocks", type=int, default=1,
+                    help="the --steps timed steps are split into this many blocks of (nearly) equal length, each between "
+                         "barriers; value and ms_per_step = the median block's time per step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (uint8 frames, colour and inverse-"
+                         "depth images) as DIR/<name>.npy in float32; beyond 60 MiB in all, a fixed seeded sample of each")
     ap.add_argument("--batch", type=int, default=8,
                     help="frames per step: ONE gsr_forward_batch call whose launches span them (include/gsr.h; 1..8)")
     ap.add_argument("--streams", type=int, default=3,
@@ -64,6 +66,8 @@ def parse():
         a.batch, a.streams = 1, a.in_flight
     if not 1 <= a.batch <= 8 or a.streams < 1:
         ap.error("--batch must be 1..8, --streams >= 1")
+    if a.steps < 1 or a.blocks < 1:
+        ap.error("--steps and --blocks must be >= 1")
     return a
 
 
@@ -141,11 +145,13 @@ def main():
     true_stats = ref_r.stats()
     del ref_r
     kw = dict(shs=m_shs, scales=m_sc, rotations=m_rot, bg=bg, layout=lay)
+    set_outs = [None] * G  # per renderer set: the (color, radii, invdepth) buffers its steps write (--dump-outputs)
 
     def group(j):
         """Step j: the B frames of output slots j B .. j B + B - 1 on renderer set j mod G."""
         base = (j % n_groups) * B
-        mcs[j % G].render([cam] * B, m_means, m_op, rgb8_out=[fg.frames[base + b] for b in range(B)], **kw)
+        set_outs[j % G] = mcs[j % G].render([cam] * B, m_means, m_op, rgb8_out=[fg.frames[base + b] for b in range(B)],
+                                            **kw)
 
     def frame1():
         r1.render(cam, m_means, m_op, rgb8_out=one_rgb8, **kw)
@@ -216,18 +222,21 @@ def main():
         step(i)
     barrier()
 
-    # ---- timed region: exactly K steps between barriers, block after block: at ~0.3 ms a step one block of the driver's
-    # K is a few milliseconds, so at least --blocks of them and --min-seconds are timed; the line carries the median
-    # block, the spread and the total-time figure
-    block_s, done = [], 0
-    while len(block_s) < max(1, args.blocks) or (sum(block_s) < args.min_seconds and len(block_s) < 400):
+    # ---- timed region: exactly K = --steps steps, as --blocks blocks of (nearly) equal length between barriers (a caller
+    # sizes K from ms_per_step); the line carries the median block's time per step, the spread and the total-time figure
+    n_blocks = min(args.blocks, args.steps)
+    block_s, block_n, done = [], [], 0
+    for k in range(n_blocks):
+        n_k = args.steps * (k + 1) // n_blocks - done
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(n_k):
             step(done + i)
         barrier()
         block_s.append(time.perf_counter() - t0)
-        done += args.steps
-    elapsed = sorted(block_s)[len(block_s) // 2]
+        block_n.append(n_k)
+        done += n_k
+    step_s = sorted(s / n for s, n in zip(block_s, block_n))
+    elapsed = step_s[len(step_s) // 2] * args.steps  # (K steps at the median block's rate)
     # Every frame slot is checked AGAIN behind the timed region, byte for byte against the default exact-mode frame: the
     # routes a static camera earns only after several balanced frames (kept splitters taken blind, buckets of 1024 records,
     # the previous frame's placement cuts, cooperative quadrants dealt by last frame's costs) are engaged in the timed
@@ -237,6 +246,11 @@ def main():
         if not torch.equal(fg.frames[b], ref_rgb8):
             raise SystemExit(f"frame slot {b} differs from the default frame AFTER the timed region: result invalid")
         verified_after += 1
+    if args.dump_outputs and rank == 0:
+        j = (done - 1) % n_groups  # the last timed step: its slots, and the buffers of its renderer set
+        color, _, invd = zip(*set_outs[j % G])
+        dump_outputs(args.dump_outputs, {"rgb8": fg.frames[j * B:(j + 1) * B], "color": torch.stack(color),
+                                         "invdepth": torch.stack(invd)})
 
     # ---- the dominant kernel's launch duration, HIP events on its launch stream: (a) the step's own launch (B frames
     # per launch), eager on one stream; (b) one frame per launch.  Every stage of both (events cannot be recorded inside
@@ -367,7 +381,7 @@ def main():
                         rocprof_ms = {"file": os.path.relpath(path, ROOT), "avg_ms": float(row["AverageNs"]) * 1e-6}
         except Exception:  # noqa: BLE001
             rocprof_ms = None
-        total_fps = world * B * args.steps * len(block_s) / sum(block_s)
+        total_fps = world * B * args.steps / sum(block_s)
         out = {
             "metric": "rendered frames/sec @640x480, 1.5M Gaussians",
             "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -389,7 +403,8 @@ def main():
                 "comparability": "rounds 1-3: value = frames / total time, one frame per step, 1-3 frames in flight on "
                                  "streams; round 4: median of 5 blocks, 3 or 4 stream lanes picked by a trial in the run; "
                                  "round 5: fixed arrangement (flags --batch / --streams), median of >= 25 blocks, "
-                                 "total-time figure beside it",
+                                 "total-time figure beside it; since then: exactly --steps timed steps, one block "
+                                 "unless --blocks splits them",
                 # the same frame: strictly one at a time / the step's launches on one stream / camera turned every frame
                 "one_frame_in_flight_frames_per_s": one_fps,
                 "one_stream_frames_per_s": one_stream_fps,
@@ -398,9 +413,8 @@ def main():
                                  f"(gsworld_amd/layout.py, {layout_s:.3f} s on this box, outside the timed region): "
                                  "preprocess skips the blocks of 256 Gaussians no tile can see; image, radii and tie "
                                  "order unchanged") if lay is not None else "model as given (--no-layout)",
-                "timed_blocks": {"blocks": len(block_s), "steps_each": args.steps, "seconds": sum(block_s),
-                                 "frames_per_s_min_median_max": [world * B * args.steps / max(block_s), fps,
-                                                                 world * B * args.steps / min(block_s)],
+                "timed_blocks": {"blocks": len(block_s), "steps_each": block_n, "seconds": sum(block_s),
+                                 "frames_per_s_min_median_max": [world * B / step_s[-1], fps, world * B / step_s[0]],
                                  "frames_per_s_total_time": total_fps, "value_is": "median block"},
                 "frame_gather": (f"RCCL {args.collective} of uint8 frames every {K_g} frames "
                                  f"(backend {dist.get_backend()}, {dist.get_world_size()} ranks)") if world > 1 else "none",
@@ -452,6 +466,26 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: the arrays' bytes in all, under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, tensors, seed=0):
+    """Writes every tensor as ``out_dir/<name>.npy`` in float32.  When they hold more than DUMP_BYTES in all, each is
+    written as the same fraction of its elements instead: the flattened values at the sorted indices
+    ``numpy.random.default_rng(seed).choice(size, k, replace=False)`` -- fixed for a given shape, so that the files of two
+    builds compare element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32) for name, t in tensors.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            k = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def _time_frames(torch, enqueue, steps, warmup=10):

@@ -325,10 +325,10 @@ def test_frame_gather_logs_are_bounded():
     assert len(fg.waits) == 0 and fg.waits.maxlen == 4096
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/gsworld"), reason="the reference tree is only present in the authoring container")
 def test_xarm6_rollout_fixture_is_what_its_script_writes(tmp_path):
-    """tests/golden/xarm6_rollout.npz against a fresh run of tools/make_xarm6_rollout.py on the reference's URDF and
-    constants (authoring container only): the committed fixture is that script's output, array for array."""
+    """tests/golden/xarm6_rollout.npz against a fresh run of tools/make_xarm6_rollout.py on the URDF joint table and
+    constants it took from the reference (tests/golden/xarm6_kinematics.npz, written by the same script): the committed
+    fixture is that script's output, array for array."""
     import importlib.util
 
     import numpy as np
@@ -338,7 +338,7 @@ def test_xarm6_rollout_fixture_is_what_its_script_writes(tmp_path):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     out = str(tmp_path / "rollout.npz")
-    mod.main(out)
+    mod.main(out, inputs=os.path.join(root, "tests", "golden", "xarm6_kinematics.npz"))
     a, b = np.load(out), np.load(os.path.join(root, "tests", "golden", "xarm6_rollout.npz"))
     assert sorted(a.files) == sorted(b.files)
     for k in a.files:
