@@ -247,6 +247,54 @@ def run_packed_batch(pack, device):
         check(lib().gsr_forward_batch(B, St, In, Out, Buf, caps, _stream(device)))
 
 
+def pack_maps(frames, binding: str = "auto"):
+    """The arguments of one ``gsr_render_maps`` call (include/gsr.h) for these frames, built once: a loop that asks for the
+    maps of the same lanes step after step keeps the pack while no state buffer moves.  ``frames``: dicts with ``settings``
+    (the frame's GsrSettings), ``P``, ``permuted``, ``r_capacity``, ``geom`` / ``binning`` / ``image`` (state tensors),
+    ``labels`` ((P,) float32 or None), ``depth_scale``, ``out_label`` ((H,W) int16 or None), ``out_depth`` ((H,W) float32 or
+    None).  ``binding``: "auto" (the compiled one when built), "ext" or "ctypes" -- the same library call either way."""
+    def ptr(t):
+        return int(t.data_ptr()) if t is not None and t.numel() else 0
+
+    vals = []
+    for f in frames:
+        st = f["settings"]
+        vals.append((tuple(getattr(st, n) for n, _ in GsrSettings._fields_), int(f["P"]), int(bool(f["permuted"])),
+                     int(f["r_capacity"]), ptr(f["geom"]), ptr(f["binning"]), ptr(f["image"]), ptr(f.get("labels")),
+                     float(f.get("depth_scale", 1.0)), ptr(f.get("out_label")), ptr(f.get("out_depth"))))
+    use_ext = _ext is not None and hasattr(_ext, "render_maps") if binding == "auto" else binding == "ext"
+    if use_ext:
+        if _ext is None or not hasattr(_ext, "render_maps"):
+            raise RuntimeError("the compiled binding (gsworld_amd._C_ext) with render_maps is not built")
+        return ("ext", vals)
+    B = len(vals)
+    sts = (GsrSettings * max(B, 1))()
+    arr = (_lib.GsrMapFrame * max(B, 1))()
+    for k, v in enumerate(vals):
+        sts[k] = GsrSettings(*v[0])
+        arr[k] = _lib.GsrMapFrame(C.sizeof(_lib.GsrMapFrame), C.pointer(sts[k]), v[1], v[2], v[3], v[4] or None, v[5] or None,
+                                  v[6] or None, v[7] or None, v[8], v[9] or None, v[10] or None)
+    return ("ctypes", (B, arr, sts))
+
+
+def run_maps(pack, device) -> None:
+    """Enqueues the ``gsr_render_maps`` call of :func:`pack_maps` on the current stream of ``device`` (capturable)."""
+    kind, p = pack
+    dev = torch.device(device)
+    if kind == "ext":
+        _ext.render_maps(dev.index if dev.index is not None else torch.cuda.current_device(), p)
+        return
+    B, arr, _ = p
+    with torch.cuda.device(dev):
+        check(lib().gsr_render_maps(B, arr, _stream(dev)))
+
+
+def render_maps(frames, device, binding: str = "auto") -> None:
+    """Segmentation / depth maps of rendered frames from their state (``gsr_render_maps``): :func:`pack_maps` +
+    :func:`run_maps`."""
+    run_maps(pack_maps(frames, binding), device)
+
+
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                         prefiltered, antialiasing, debug, sh_rest=None, param_space: int = 0):

@@ -119,6 +119,14 @@ class GsrStateView(C.Structure):
         "ranges", "final_T", "n_contrib")]
 
 
+class GsrMapFrame(C.Structure):
+    """One frame of ``gsr_render_maps`` (include/gsr.h): segmentation / depth maps from the frame's own state."""
+    _fields_ = [("struct_size", C.c_int32), ("settings", C.POINTER(GsrSettings)), ("P", C.c_int32),
+                ("permuted", C.c_int32), ("r_capacity", C.c_int64), ("geom", C.c_void_p), ("binning", C.c_void_p),
+                ("image", C.c_void_p), ("labels", C.c_void_p), ("depth_scale", C.c_float), ("out_label", C.c_void_p),
+                ("out_depth", C.c_void_p)]
+
+
 class GsrProfile(C.Structure):
     _fields_ = [("frames", C.c_int32), ("stage_ms", C.c_double * 5)]
 
@@ -187,6 +195,8 @@ def lib() -> C.CDLL:
     L.gsr_pinned_device_address.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.gsr_stage_step.restype = C.c_int
     L.gsr_stage_step.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.gsr_render_maps.restype = C.c_int
+    L.gsr_render_maps.argtypes = [C.c_int32, C.POINTER(GsrMapFrame), C.c_void_p]
     L.gsr_profile_enable.restype = C.c_int
     L.gsr_profile_enable.argtypes = [C.c_int]
     L.gsr_profile_collect.restype = C.c_int

@@ -39,11 +39,25 @@ def _to_mirror(dst: torch.Tensor, dst_np, src: torch.Tensor) -> None:
         dst.copy_(src.detach().to("cpu", torch.float32).reshape(dst.shape))
 
 
+MAP_KINDS = ("segmentation", "depth")
+
+
+def check_map_labels(labels: torch.Tensor) -> torch.Tensor:
+    """The per-Gaussian semantic labels of a segmentation map as ``gsr_render_maps`` reads them: (P,) float32, dense, on the
+    labels' device.  Every label must be an integral value inside int16 (the map stores ``(int16)(int)label``); anything else
+    raises ``ValueError`` -- once, when a loop is built, not per frame."""
+    lab = labels.detach().reshape(-1).to(torch.float32).contiguous()
+    if lab.numel() and not bool(torch.all(torch.isfinite(lab) & (lab == torch.round(lab)) & (lab >= -32768) & (lab <= 32767))):
+        raise ValueError("segmentation maps need integral semantic labels in the int16 range [-32768, 32767]")
+    return lab
+
+
 class ClosedLoopRenderer:
     def __init__(self, raw, part_labels: dict, cameras: dict, scaled_parts=(), num_envs: int = 1, device="cuda",
                  background=None, fuse_transform: bool = True, growth: float = 2.0, bound_capacity="auto",
                  layout: bool = True, min_capacity: int | None = None, share_model_of=None, batched: bool = True,
-                 keep_float: bool = False, block_cache: bool = True, tile_reuse: bool = True):
+                 keep_float: bool = False, block_cache: bool = True, tile_reuse: bool = True, maps=(),
+                 depth_scale: float = 1.0):
         """``raw``: :class:`gsworld_amd.scenes.RawGaussians` (or any object with the same raw parameter tensors, e.g. a
         merged semantic model's ``_xyz`` ... under those names); ``part_labels``: part name -> semantic label(s), in
         the order the pose matrices will arrive; ``cameras``: name -> :class:`gsworld_amd.camera.ViewParams`;
@@ -79,7 +93,19 @@ class ClosedLoopRenderer:
         tracked objects cover, now or a step ago.  Same frames, bit for bit.  ``False`` for a caller that writes into them.
         ``batched`` (default): the E x C frames of a step go through ``gsr_forward_batch`` -- one set of launches on the
         step's stream whose grids span the frames -- instead of one pipeline per frame on its own stream
-        (:class:`gsworld_amd.renderer.MultiCameraRenderer`); same frames bit for bit (tests/test_batch_gpu.py)."""
+        (:class:`gsworld_amd.renderer.MultiCameraRenderer`); same frames bit for bit (tests/test_batch_gpu.py).
+        ``maps``: any subset of ``("segmentation", "depth")`` -- every step then also writes per-pixel maps of the splatted
+        scene into :attr:`maps`, ``{camera: {"segmentation": (E,H,W,1) int16, "depth": (E,H,W,1) float32}}`` (the kinds
+        asked for), loop-owned buffers overwritten by the next step like :attr:`frames`; :meth:`step` still returns the
+        frames.  A pixel's label and depth are those of its median contributor, the first Gaussian after which the
+        transmittance drops below 0.5 (include/gsr.h ``gsr_render_maps``); background: label -1, depth 0.0.  Labels are the
+        model's semantics (integral, inside int16: ``ValueError`` otherwise).  Depth is ``depth_scale`` x the view depth in
+        the scene's units; for GSWorld pass ``depth_scale = 1 / scale_sim2real`` to get the simulator's metres, since
+        ``cam_maniskill2gs`` scales camera translations by ``scale_sim2real`` (gs_world_wrapper.py:298).  With the default
+        ``()`` nothing changes: no buffer, no launch, :attr:`maps` is None."""
+        maps = tuple(maps or ())
+        if any(m not in MAP_KINDS for m in maps) or len(set(maps)) != len(maps):
+            raise ValueError(f"maps must be a subset of {MAP_KINDS}, got {maps!r}")
         self.device = torch.device(device)
         dev = self.device
         self.num_envs = int(num_envs)
@@ -125,6 +151,10 @@ class ClosedLoopRenderer:
             self.layout = L.layout
             self.perm = L.perm  # (position in the loop's arrays -> number in the caller's model)
         self._semantics = semantics
+        self.map_kinds = tuple(m for m in MAP_KINDS if m in maps)
+        self.depth_scale = float(depth_scale)
+        # (the labels of the loop's own arrays -- the permuted copy when laid out -- checked once)
+        self._map_labels = check_map_labels(semantics.to(dev)) if "segmentation" in self.map_kinds else None
         self.op = tf.FusedPartTransform(part_labels, semantics.to(dev), scaled_parts=scaled_parts)
         self.rescaled = len(tuple(scaled_parts)) > 0
         if self.num_envs > 1:
@@ -146,6 +176,10 @@ class ClosedLoopRenderer:
         H, W = self.cameras[0].image_height, self.cameras[0].image_width
         self.frames = {n: torch.zeros((self.num_envs, c.image_height, c.image_width, 3), dtype=torch.uint8, device=dev)
                        for n, c in zip(self.names, self.cameras)}
+        dts = {"segmentation": torch.int16, "depth": torch.float32}
+        self.maps = {n: {m: torch.zeros((self.num_envs, c.image_height, c.image_width, 1), dtype=dts[m], device=dev)
+                         for m in self.map_kinds} for n, c in zip(self.names, self.cameras)} if self.map_kinds else None
+        self._maps_pack = None  # (the gsr_render_maps arguments of the lanes, and the state addresses they were built for)
         self.bg = torch.zeros(3, device=dev) if background is None else background.to(dev, torch.float32)
         # the loop never differentiates a frame: inference frames (GsrSettings.forward_only), no radii array
         lanes = self.num_envs * len(self.cameras)
@@ -296,6 +330,7 @@ class ClosedLoopRenderer:
                               shs_rest=self.features_rest, scales=self.scaling, rotations=self.rotation,
                               param_space=RAW_SCALES | RAW_ROTATIONS | self._model_version, bg=self.bg, per_lane=per_lane,
                               layout=self.layout)
+            self._run_maps()
             return
         if self.rescaled:
             xyz, rot, scaling = self.op.apply(self.xyz, self.rotation, self.matrices, self.scales, scaling=self.scaling)
@@ -319,6 +354,30 @@ class ClosedLoopRenderer:
             self.multi.render(views, None, self.opacity, rgb8_out=outs, shs=self.features_dc,
                               shs_rest=self.features_rest, param_space=RAW_SCALES | RAW_ROTATIONS, bg=self.bg,
                               per_lane=per_lane)
+        self._run_maps()
+
+    def _run_maps(self):
+        """The step's segmentation / depth maps (``maps``), behind its frames on the current stream: one ``gsr_render_maps``
+        call over every lane (capturable).  The argument pack is kept while no lane's state buffer moves."""
+        if self.maps is None:
+            return
+        lanes = self.multi.lanes
+        key = tuple(l._map_key() for l in lanes)
+        if self._maps_pack is None or self._maps_pack[0] != key:
+            C = len(self.cameras)
+            frames = []
+            for k, lane in enumerate(lanes):
+                e, name = k // C, self.names[k % C]
+                m = self.maps[name]
+                seg, dep = m.get("segmentation"), m.get("depth")
+                f, _, _ = lane._map_frame(self._map_labels if seg is not None else None, self.depth_scale,
+                                          seg[e].view(seg.shape[1], seg.shape[2]) if seg is not None else None,
+                                          dep[e].view(dep.shape[1], dep.shape[2]) if dep is not None else None)
+                if dep is None:
+                    f["out_depth"] = None  # (_map_frame allocated one: the loop was not asked for depth)
+                frames.append(f)
+            self._maps_pack = (key, _C.pack_maps(frames))
+        _C.run_maps(self._maps_pack[1], self.device)
 
     def _flush(self):
         """Host-side changes since the last flush go up in as few copies as possible: one contiguous run of the staging
@@ -511,6 +570,7 @@ class ClosedLoopRenderer:
             else:
                 self._launch_stage(k, int(self._stage.numel()))
                 self.multi.rerun(self._pack)
+            self._run_maps()
             self._slot_release(k, ensure)
         elif self._graphs is not None:
             # this step's host values travel INSIDE its graph: the whole mirror into the next pinned slot (a host copy of a
@@ -524,6 +584,7 @@ class ClosedLoopRenderer:
         elif self._pack is not None and self.fuse_transform and self._table is not None:
             self._flush()
             self.multi.rerun(self._pack)  # (the frames' arguments have not changed: device buffers, written by the flush)
+            self._run_maps()
         else:
             self._gpu_step()
             self._pack = self.multi.last_pack if self.fuse_transform and self._table is not None else None
@@ -724,6 +785,8 @@ class PipelinedClosedLoop:
     def __init__(self, raw, part_labels: dict, cameras: dict, depth: int = 2, **kw):
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        if kw.get("maps"):
+            raise ValueError("PipelinedClosedLoop does not render segmentation / depth maps: use ClosedLoopRenderer(maps=...)")
         first = ClosedLoopRenderer(raw, part_labels, cameras, **kw)
         self.loops = [first] + [ClosedLoopRenderer(raw, part_labels, cameras, share_model_of=first, **kw)
                                 for _ in range(depth - 1)]

@@ -463,6 +463,84 @@ int gsr_plan_query(const GsrSettings *st, int32_t P, int32_t permuted, int64_t r
     return GSR_OK;
 }
 
+// Segmentation / depth maps behind rendered frames (include/gsr.h; maps.hip).  The state's layout is the plan's: where the
+// lists live and what they are lists of (per tile, or per super-tile with tau and the tile rect in the records).
+int gsr_render_maps(int32_t B, const GsrMapFrame *frames, void *stream_) {
+    if (B < 0 || (B > 0 && !frames)) {
+        gsr_set_error("gsr_render_maps: null frame array or negative B");
+        return GSR_E_INVALID;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    std::vector<GsrMapsArgs> jobs;
+    jobs.reserve((size_t)B);
+    bool debug = false;
+    for (int k = 0; k < B; k++) {
+        const GsrMapFrame &f = frames[k];
+        if (f.struct_size != (int32_t)sizeof(GsrMapFrame)) {
+            gsr_set_error("gsr_render_maps: frame %d: struct_size %d, this library's GsrMapFrame has %d bytes", k,
+                          (int)f.struct_size, (int)sizeof(GsrMapFrame));
+            return GSR_E_INVALID;
+        }
+        const GsrSettings *st = f.settings;
+        if (!st || st->image_width <= 0 || st->image_height <= 0 || f.P < 0) {
+            gsr_set_error("gsr_render_maps: frame %d: null settings, empty image or negative P", k);
+            return GSR_E_INVALID;
+        }
+        if (f.out_label && !f.labels) {
+            gsr_set_error("gsr_render_maps: frame %d: out_label needs labels", k);
+            return GSR_E_INVALID;
+        }
+        if (f.P > 0 && (!f.geom || !f.binning || !f.image)) {
+            gsr_set_error("gsr_render_maps: frame %d: the frame's three state buffers are required", k);
+            return GSR_E_INVALID;
+        }
+        // (the plan gsr_forward made for the frame: a frame it would refuse has no state to read)
+        GsrInputs in;
+        memset(&in, 0, sizeof(in));
+        in.P = f.P;
+        static const int32_t one = 0;
+        in.orig_index = f.permuted ? &one : nullptr;  // (only ever compared with NULL)
+        Plan p;
+        if (make_plan(st, &in, f.r_capacity, p) != GSR_OK) {
+            gsr_set_error("gsr_render_maps: frame %d is not one gsr_forward renders (permuted model on another path, or "
+                          "r_capacity beyond 32 bits)", k);
+            return GSR_E_INVALID;
+        }
+        debug = debug || st->debug != 0;
+        const size_t n = (size_t)p.W * p.H;
+        if (f.P == 0) {  // (nothing was rendered: the background everywhere -- int16 -1 is the byte pattern 0xFF)
+            if ((f.out_label && hipMemsetAsync(f.out_label, 0xFF, n * sizeof(int16_t), stream) != hipSuccess) ||
+                (f.out_depth && hipMemsetAsync(f.out_depth, 0, n * sizeof(float), stream) != hipSuccess)) {
+                gsr_set_error("gsr_render_maps: hipMemsetAsync failed");
+                return GSR_E_HIP;
+            }
+            continue;
+        }
+        if (!f.out_label && !f.out_depth) continue;
+        // (header, splat records, point list and ranges sit where every layout -- lean or not, any capacity -- carves them)
+        const GeomState g = GeomState::carve((char *)f.geom, f.P, p.tiles);
+        const BinningState b = BinningState::carve((char *)f.binning, 1);
+        const ImageState s = ImageState::carve((char *)f.image, p.W, p.H);
+        GsrMapsArgs a;
+        a.ranges = s.ranges;
+        a.point_list = b.gidx[0];
+        a.splat = g.splat;
+        a.hdr = g.hdr;
+        a.labels = f.labels;
+        a.out_label = f.out_label;
+        a.out_depth = f.out_depth;
+        a.depth_scale = f.depth_scale;
+        a.W = p.W;
+        a.H = p.H;
+        a.gx = p.tiles_x;
+        a.gy = p.tiles_y;
+        a.super = p.super ? 1 : 0;
+        jobs.push_back(a);
+    }
+    if (jobs.empty()) return GSR_OK;
+    return gsr_launch_maps((int)jobs.size(), jobs.data(), debug, stream);
+}
+
 int gsr_profile_enable(int mode) {
     if (mode < 0 || mode > 2) {
         gsr_set_error("gsr_profile_enable: mode must be 0, 1 or 2");

@@ -475,6 +475,20 @@ struct GsrFrame {
     bool td;                    // ... and its compositor the tiles none of the recomputed Gaussians touches (render.hip)
 };
 
+// One frame of the segmentation / depth pass (maps.hip; gsr_render_maps resolves it from a GsrMapFrame and the frame's plan).
+struct GsrMapsArgs {
+    const uint2 *ranges;        // the frame's lists: per tile, or per super-tile (super)
+    const uint32_t *point_list;
+    const float4 *splat;
+    const GsrHeader *hdr;       // (the overflow flag: such a frame gets background maps)
+    const float *labels;        // (P) or nullptr (then out_label is nullptr)
+    int16_t *out_label;         // (H,W) or nullptr
+    float *out_depth;           // (H,W) or nullptr
+    float depth_scale;
+    int W, H, gx, gy;
+    int super;                  // 1: super-tile lists, tau and the tile rect in the records (inference frames, default path)
+};
+
 // ---- error plumbing ------------------------------------------------------------------------------------
 void gsr_set_error(const char *fmt, ...);
 int gsr_check_launch(const char *what, bool debug, hipStream_t stream);
@@ -520,6 +534,8 @@ int gsr_render_cus_per_xcd();  // CUs of one XCD (the quadrant deal of gsr_quad_
 int gsr_render_coop_blocks(const GsrSettings &st, int num_tiles, int frames);
 int gsr_launch_render(int B, const GsrFrame *fr, bool order_ready, bool split_ready, bool super_tiles, int coop_blocks,
                       hipStream_t stream);
+// segmentation / depth maps behind a frame (maps.hip): B frames, cut into launches of GSR_MAX_BATCH
+int gsr_launch_maps(int B, const GsrMapsArgs *frames, bool debug, hipStream_t stream);
 int gsr_launch_tile_count(const GsrSettings &st, int32_t P, const GeomState &g, const ImageState &img,
                           uint32_t r_capacity, bool debug, hipStream_t stream);
 int gsr_launch_tile_place(const GsrSettings &st, int32_t P, const GeomState &g, const BinningState &b,

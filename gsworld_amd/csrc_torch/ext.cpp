@@ -331,6 +331,59 @@ std::tuple<int64_t, int64_t, int64_t> frame_stats(const torch::Tensor &geom) {
     return {s.num_visible, s.num_rendered, (int64_t)s.overflow};
 }
 
+// ---- segmentation / depth maps of rendered frames (gsworld_amd._C.render_maps) ----------------------------------------
+// One tuple per frame: (GsrSettings as its 17 fields in declaration order, P, permuted, r_capacity, geom, binning, image,
+// labels, depth_scale, out_label, out_depth) -- buffers as device addresses (0 = NULL), as the ctypes path passes them.
+void render_maps(int64_t device_index, const py::list &frames) {
+    const size_t B = frames.size();
+    std::vector<GsrSettings> st(B);
+    std::vector<GsrMapFrame> mf(B);
+    auto P = [](const py::handle &h) { return reinterpret_cast<void *>((uintptr_t)h.cast<int64_t>()); };
+    for (size_t k = 0; k < B; k++) {
+        const py::tuple t = frames[k].cast<py::tuple>();
+        TORCH_CHECK(t.size() == 11, "render_maps: a frame is a tuple of 11 values, got ", t.size());
+        const py::tuple s = t[0].cast<py::tuple>();
+        TORCH_CHECK(s.size() == 17, "render_maps: GsrSettings has 17 fields, got ", s.size());
+        GsrSettings &x = st[k];
+        std::memset(&x, 0, sizeof(x));
+        x.image_height = s[0].cast<int>();
+        x.image_width = s[1].cast<int>();
+        x.tanfovx = s[2].cast<float>();
+        x.tanfovy = s[3].cast<float>();
+        x.scale_modifier = s[4].cast<float>();
+        x.sh_degree = s[5].cast<int>();
+        x.sh_coeffs = s[6].cast<int>();
+        x.prefiltered = s[7].cast<int>();
+        x.antialiasing = s[8].cast<int>();
+        x.debug = s[9].cast<int>();
+        x.near_plane = s[10].cast<float>();
+        x.binning_path = s[11].cast<int>();
+        x.render_variant = s[12].cast<int>();
+        x.render_blocks_per_cu = s[13].cast<int>();
+        x.depth_sort = s[14].cast<int>();
+        x.render_split = s[15].cast<int>();
+        x.forward_only = s[16].cast<int>();
+        GsrMapFrame &f = mf[k];
+        std::memset(&f, 0, sizeof(f));
+        f.struct_size = (int32_t)sizeof(GsrMapFrame);
+        f.settings = &st[k];
+        f.P = t[1].cast<int32_t>();
+        f.permuted = t[2].cast<int32_t>();
+        f.r_capacity = t[3].cast<int64_t>();
+        f.geom = P(t[4]);
+        f.binning = P(t[5]);
+        f.image = P(t[6]);
+        f.labels = static_cast<const float *>(P(t[7]));
+        f.depth_scale = t[8].cast<float>();
+        f.out_label = static_cast<int16_t *>(P(t[9]));
+        f.out_depth = static_cast<float *>(P(t[10]));
+    }
+    const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int rc = gsr_render_maps((int32_t)B, mf.data(), current_stream(dev));
+    TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+}
+
 // ---- upstream's three functions ------------------------------------------------------------------------------------
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 rasterize_gaussians(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
@@ -520,5 +573,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("run", &StepPack::run)
         .def("run_staged", &StepPack::run_staged);
     m.def("frame_stats", &frame_stats);
+    m.def("render_maps", &render_maps);
     m.def("version", []() { return std::string(gsr_version()); });
 }

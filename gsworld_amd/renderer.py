@@ -90,6 +90,7 @@ class FrameRenderer:
             if lib().gsr_pinned_device_address(C.c_void_p(self._mirror.data_ptr()), C.byref(d)) == 0 and d.value:
                 self._mirror_dev = int(d.value)
         self.overflows_handled = 0  # (callers that re-render on overflow keep their own tally against overflows_seen)
+        self._map_meta = None  # (settings, P, permuted, r_capacity) of the last frame enqueued
 
     def _capacity_for(self, num_rendered: int) -> int:
         return max(int(num_rendered * self.growth), self.min_capacity, 1 << 16)
@@ -221,6 +222,12 @@ class FrameRenderer:
             overflow_mirror=(self._mirror_dev or 0) if not self.bounded else 0)
         if not self.want_float and outputs is None:
             color = invd = None  # (what the caller gets back; the call holds the empty tensors = NULL images)
+        # (what render_maps needs to find its way through the frame's state: the plan follows from these)
+        # (the settings as the library receives them: the call adds forward_only and the A/B selectors to `st`)
+        mst = GsrSettings.from_buffer_copy(st)
+        (mst.binning_path, mst.render_variant, mst.render_blocks_per_cu, mst.depth_sort, mst.render_split,
+         mst.forward_only) = _C._tuning_list(self.forward_only)
+        self._map_meta = (mst, P, layout is not None and layout[1] is not None, cap)
         return call, color, radii, invd
 
     def _finish(self, cap: int, stats=None):
@@ -230,6 +237,50 @@ class FrameRenderer:
         if self._mirror is not None and self._mirror_dev is None and not self.bounded and self.geom.numel() >= 256:
             # (of_magic, overflow_frames): the last two words of the 256-byte frame header (csrc/gsr_internal.h GsrHeader)
             self._mirror.copy_(self.geom[248:256].view(torch.int32), non_blocking=True)
+
+    def _map_frame(self, labels, depth_scale, out_label, out_depth):
+        """The ``gsr_render_maps`` frame of this lane's last frame (outputs allocated where None; ``out_label`` only with
+        ``labels``).  -> (frame dict of :func:`gsworld_amd._C.pack_maps`, label, depth)."""
+        if self._map_meta is None:
+            raise RuntimeError("render_maps: no frame has been rendered on this renderer yet")
+        st, P, permuted, cap = self._map_meta
+        H, W = st.image_height, st.image_width
+        dev = self.device
+        if labels is not None:
+            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.float32 or labels.device != dev or \
+                    labels.numel() != P or not labels.is_contiguous():
+                raise ValueError(f"labels must be a dense ({P},) float32 tensor on {dev}")
+            if out_label is None:
+                out_label = torch.empty((H, W), dtype=torch.int16, device=dev)
+        elif out_label is not None:
+            raise ValueError("out_label needs labels")
+        if out_depth is None:
+            out_depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+        for t, dt, what in ((out_label, torch.int16, "out_label"), (out_depth, torch.float32, "out_depth")):
+            if t is not None and (t.dtype != dt or t.device != dev or t.numel() != H * W or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a dense {H * W}-element {dt} tensor on {dev} ((H,W) of the frame)")
+        f = dict(settings=st, P=P, permuted=permuted, r_capacity=cap, geom=self.geom, binning=self.binning, image=self.image,
+                 labels=labels if out_label is not None else None, depth_scale=float(depth_scale), out_label=out_label,
+                 out_depth=out_depth)
+        return f, out_label, out_depth
+
+    def _map_key(self):
+        """What a kept ``gsr_render_maps`` argument pack of this lane depends on (state addresses, the last frame's plan inputs)."""
+        st, P, permuted, cap = self._map_meta
+        return (self.geom.data_ptr(), self.binning.data_ptr(), self.image.data_ptr(), P, permuted, cap,
+                tuple(getattr(st, n) for n, _ in GsrSettings._fields_))
+
+    def render_maps(self, labels=None, depth_scale: float = 1.0, out_label=None, out_depth=None):
+        """Segmentation and depth maps of this renderer's LAST frame, computed from its state on the current stream (after
+        the frame; no synchronisation): per pixel the label and ``depth_scale`` x view depth of the median contributor -- the
+        first Gaussian after which the transmittance drops below 0.5 (include/gsr.h ``gsr_render_maps``).  Background (the
+        transmittance never drops below 0.5, or the frame overflowed its capacity): label -1, depth 0.0.  ``labels``: (P,)
+        float32 per Gaussian of the arrays the frame was rendered from (the permuted copy of a laid-out model), or None (no
+        label map).  ``out_label`` ((H,W) int16) / ``out_depth`` ((H,W) float32): written if given, else allocated.
+        -> (label (H,W) int16 | None, depth (H,W) float32)."""
+        f, lab, dep = self._map_frame(labels, depth_scale, out_label, out_depth)
+        _C.render_maps([f], self.device)
+        return lab, dep
 
     def overflows_seen(self) -> int:
         """Frames on this state whose instance count exceeded the capacity, as far as the host has been told (no
@@ -406,6 +457,24 @@ class MultiCameraRenderer:
                         cur.wait_stream(st)
             for lane, cap in caps:
                 lane._finish(cap)
+        return outs
+
+    def render_maps(self, labels=None, depth_scale: float = 1.0, out_label=None, out_depth=None):
+        """:meth:`FrameRenderer.render_maps` of every lane's last frame in ONE ``gsr_render_maps`` call on the current
+        stream.  ``labels``: one (P,) tensor for all lanes, or a list per lane; ``out_label`` / ``out_depth``: None or lists
+        per lane.  -> ``[(label | None, depth)]`` per lane."""
+        n = len(self.lanes)
+        per = lambda x: list(x) if isinstance(x, (list, tuple)) else [x] * n  # noqa: E731
+        labs, ols, ods = per(labels), (list(out_label) if out_label is not None else [None] * n), \
+            (list(out_depth) if out_depth is not None else [None] * n)
+        if len(labs) != n or len(ols) != n or len(ods) != n:
+            raise ValueError(f"expected one entry per lane ({n})")
+        frames, outs = [], []
+        for lane, lab, ol, od in zip(self.lanes, labs, ols, ods):
+            f, a, b = lane._map_frame(lab, depth_scale, ol, od)
+            frames.append(f)
+            outs.append((a, b))
+        _C.render_maps(frames, self.device)
         return outs
 
     def ensure_valid(self, rerender) -> list:

@@ -14,6 +14,9 @@
  *   gsr_ssim_backward      <->  fused_ssim_cuda.fusedssim_backward
  *   gsr_transform_gaussians<->  the per-step rigid transform of GSWorld itself
  *                               (gs_world_wrapper.py:110-162,244-265 + gsworld/utils/gs_utils.py:283-385)
+ *   gsr_render_maps        <->  the segmentation / depth observations (obs_mode rgb+segmentation, rgbd) that the wrapper
+ *                               leaves to SAPIEN's meshes (gs_world_wrapper.py:184,196,222 overwrite 'rgb' only): here
+ *                               from the splatted scene itself, consistent with the frame
  *
  * Conventions: plain pointers and sizes only (no torch types); every data pointer is DEVICE memory on the
  * current HIP device unless marked [host]; all inputs are borrowed, contiguous, float32; `stream` is a
@@ -301,6 +304,34 @@ typedef struct GsrStateView {
 } GsrStateView;
 int gsr_state_view(int32_t P, int32_t width, int32_t height, int64_t r_capacity_or_R, const void *geom,
                    const void *binning, const void *image, GsrStateView *view);
+
+/*
+ * Segmentation and depth maps of rendered frames, from the frames' own state (one pass behind the frames, on `stream`; the
+ * colour compositor is not touched).  A pixel walks the depth-ordered list of its 16 x 16 tile as the compositor does --
+ * alpha = min(0.99, opacity exp(power)), skipped when power > 0 or alpha < 1/255, T <- T (1 - alpha) -- and its MEDIAN
+ * CONTRIBUTOR is the first composited Gaussian after which T (1 - alpha) < 0.5:
+ *   out_label[pixel] = (int16)(int)labels[g] of it, or -1 where the transmittance never drops below 0.5;
+ *   out_depth[pixel] = depth_scale / (1 / view depth) of it, or 0.0 there (ManiSkill's background depth).
+ * Labels are numbered as the arrays the frame was rendered from (a permuted copy when GsrInputs.orig_index was given).  A
+ * frame that overflowed its binning capacity gets background maps, as its image shows the background (read on the device:
+ * nothing is read back).  No allocation, no synchronisation: the call can be captured into a hipGraph.  Frame k is
+ * described by frames[k]; B frames go through launches of up to GSR_MAX_FRAMES_PER_LAUNCH frames.  Every frame the default
+ * path of gsr_forward / gsr_forward_batch rendered is accepted (exact or capacity mode, forward_only or not, permuted or
+ * not); the state's layout follows from the same plan gsr_forward makes (gsr_plan_query), and a frame gsr_forward would
+ * refuse is refused (GSR_E_INVALID).  A frame with P == 0 gets background maps.
+ */
+typedef struct GsrMapFrame {
+    int32_t struct_size;            /* sizeof(GsrMapFrame): the library rejects a mismatch (GSR_E_INVALID) */
+    const GsrSettings *settings;    /* [host] as the frame was rendered */
+    int32_t P; int32_t permuted;    /* permuted: GsrInputs.orig_index was given */
+    int64_t r_capacity;             /* as passed to gsr_forward / gsr_forward_batch (<= 0: exact mode) */
+    const void *geom, *binning, *image;  /* the frame's state buffers */
+    const float *labels;            /* (P) or NULL (then out_label must be NULL) */
+    float depth_scale;
+    int16_t *out_label;             /* (H,W) or NULL */
+    float *out_depth;               /* (H,W) or NULL */
+} GsrMapFrame;
+int gsr_render_maps(int32_t B, const GsrMapFrame *frames, void *stream);
 
 /*
  * Optional stage timing with HIP events recorded on the caller's stream (what bench.py's roofline uses).
