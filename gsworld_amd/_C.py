@@ -295,6 +295,53 @@ def render_maps(frames, device, binding: str = "auto") -> None:
     run_maps(pack_maps(frames, binding), device)
 
 
+def pack_pointcloud(spec: dict, binding: str = "auto"):
+    """The arguments of one ``gsr_render_pointcloud`` call (include/gsr.h), built once: a loop that asks for the clouds of
+    the same buffers step after step keeps the pack while no buffer moves.  ``spec``: ``E``, ``C``, ``views`` (E*C dicts:
+    ``width``, ``height``, ``tanfovx``, ``tanfovy``, ``viewmatrix``, ``depth``, ``depth_scale``, ``label``, ``rgb8`` --
+    tensors or None), ``out_from_scene`` (12 floats, row-major 3 x 4), ``crop`` (None or (lo, hi)), ``exclude`` ((2048,)
+    int32 bitmap or None), ``mode``, ``K``, ``fps_candidates``, ``xyzw`` / ``rgb`` / ``segmentation`` / ``count`` (outputs),
+    ``workspace`` (uint8 tensor).  ``binding``: "auto" (the compiled one when built), "ext" or "ctypes"."""
+    def ptr(t):
+        return int(t.data_ptr()) if t is not None and t.numel() else 0
+
+    views = [(int(v["width"]), int(v["height"]), float(v["tanfovx"]), float(v["tanfovy"]), ptr(v["viewmatrix"]),
+              ptr(v["depth"]), float(v["depth_scale"]), ptr(v.get("label")), ptr(v.get("rgb8"))) for v in spec["views"]]
+    crop = spec.get("crop")
+    lo, hi = ([float(x) for x in crop[0]], [float(x) for x in crop[1]]) if crop is not None else ([0.0] * 3, [0.0] * 3)
+    ws = spec["workspace"]
+    vals = (int(spec["E"]), int(spec["C"]), views, [float(x) for x in spec["out_from_scene"]], int(crop is not None), lo, hi,
+            ptr(spec.get("exclude")), int(spec["mode"]), int(spec.get("K", 0)), int(spec.get("fps_candidates", 0)),
+            ptr(spec["xyzw"]), ptr(spec["rgb"]), ptr(spec["segmentation"]), ptr(spec["count"]), ptr(ws), int(ws.numel()))
+    use_ext = _ext is not None and hasattr(_ext, "CloudPack") if binding == "auto" else binding == "ext"
+    if use_ext:
+        if _ext is None or not hasattr(_ext, "CloudPack"):
+            raise RuntimeError("the compiled binding (gsworld_amd._C_ext) with CloudPack is not built")
+        return ("ext", _ext.CloudPack(vals))
+    arr = (_lib.GsrCloudView * len(views))(*[_lib.GsrCloudView(*v) for v in views])
+    cs = _lib.GsrCloudSpec()
+    cs.struct_size = C.sizeof(_lib.GsrCloudSpec)
+    cs.E, cs.C, cs.views = vals[0], vals[1], arr
+    cs.out_from_scene[:] = vals[3]
+    cs.crop = vals[4]
+    cs.crop_lo[:], cs.crop_hi[:] = lo, hi
+    (cs.exclude, cs.mode, cs.K, cs.fps_candidates, cs.out_xyzw, cs.out_rgb, cs.out_segmentation, cs.out_count,
+     cs.workspace, cs.workspace_bytes) = (vals[7] or None, *vals[8:11], *(v or None for v in vals[11:16]), vals[16])
+    return ("ctypes", (cs, arr))
+
+
+def run_pointcloud(pack, device) -> None:
+    """Enqueues the ``gsr_render_pointcloud`` call of :func:`pack_pointcloud` on the current stream of ``device``
+    (capturable)."""
+    kind, p = pack
+    dev = torch.device(device)
+    if kind == "ext":
+        p.run(dev.index if dev.index is not None else torch.cuda.current_device())
+        return
+    with torch.cuda.device(dev):
+        check(lib().gsr_render_pointcloud(C.byref(p[0]), _stream(dev)))
+
+
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                         prefiltered, antialiasing, debug, sh_rest=None, param_space: int = 0):

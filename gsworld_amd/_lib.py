@@ -127,6 +127,27 @@ class GsrMapFrame(C.Structure):
                 ("out_depth", C.c_void_p)]
 
 
+PC_DENSE, PC_STRIDE, PC_FPS = 0, 1, 2  # include/gsr.h GSR_PC_*
+PC_MAX_VIEWS, PC_MAX_K, PC_MAX_FPS_CANDIDATES, PC_MAX_VIEW_PIXELS = 64, 8192, 16384, 1 << 24
+
+
+class GsrCloudView(C.Structure):
+    """One (environment, camera) view of ``gsr_render_pointcloud`` (include/gsr.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("tanfovx", C.c_float), ("tanfovy", C.c_float),
+                ("viewmatrix", C.c_void_p), ("depth", C.c_void_p), ("depth_scale", C.c_float), ("label", C.c_void_p),
+                ("rgb8", C.c_void_p)]
+
+
+class GsrCloudSpec(C.Structure):
+    """The arguments of ``gsr_render_pointcloud`` / ``gsr_pointcloud_workspace`` (include/gsr.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("E", C.c_int32), ("C", C.c_int32), ("views", C.POINTER(GsrCloudView)),
+                ("out_from_scene", C.c_float * 12), ("crop", C.c_int32), ("crop_lo", C.c_float * 3),
+                ("crop_hi", C.c_float * 3), ("exclude", C.c_void_p), ("mode", C.c_int32), ("K", C.c_int32),
+                ("fps_candidates", C.c_int32), ("out_xyzw", C.c_void_p), ("out_rgb", C.c_void_p),
+                ("out_segmentation", C.c_void_p), ("out_count", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64)]
+
+
 class GsrProfile(C.Structure):
     _fields_ = [("frames", C.c_int32), ("stage_ms", C.c_double * 5)]
 
@@ -197,6 +218,10 @@ def lib() -> C.CDLL:
     L.gsr_stage_step.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.gsr_render_maps.restype = C.c_int
     L.gsr_render_maps.argtypes = [C.c_int32, C.POINTER(GsrMapFrame), C.c_void_p]
+    L.gsr_render_pointcloud.restype = C.c_int
+    L.gsr_render_pointcloud.argtypes = [C.POINTER(GsrCloudSpec), C.c_void_p]
+    L.gsr_pointcloud_workspace.restype = C.c_int
+    L.gsr_pointcloud_workspace.argtypes = [C.POINTER(GsrCloudSpec), C.POINTER(C.c_int64)]
     L.gsr_profile_enable.restype = C.c_int
     L.gsr_profile_enable.argtypes = [C.c_int]
     L.gsr_profile_collect.restype = C.c_int

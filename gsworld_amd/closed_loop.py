@@ -23,7 +23,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _C
+from . import _C, _lib
 from . import transform as tf
 from ._lib import FRAME_KEPT, RAW_ROTATIONS, RAW_SCALES, model_version
 from .renderer import MultiCameraRenderer
@@ -57,7 +57,7 @@ class ClosedLoopRenderer:
                  background=None, fuse_transform: bool = True, growth: float = 2.0, bound_capacity="auto",
                  layout: bool = True, min_capacity: int | None = None, share_model_of=None, batched: bool = True,
                  keep_float: bool = False, block_cache: bool = True, tile_reuse: bool = True, maps=(),
-                 depth_scale: float = 1.0):
+                 depth_scale: float = 1.0, pointcloud=None):
         """``raw``: :class:`gsworld_amd.scenes.RawGaussians` (or any object with the same raw parameter tensors, e.g. a
         merged semantic model's ``_xyz`` ... under those names); ``part_labels``: part name -> semantic label(s), in
         the order the pose matrices will arrive; ``cameras``: name -> :class:`gsworld_amd.camera.ViewParams`;
@@ -102,10 +102,26 @@ class ClosedLoopRenderer:
         model's semantics (integral, inside int16: ``ValueError`` otherwise).  Depth is ``depth_scale`` x the view depth in
         the scene's units; for GSWorld pass ``depth_scale = 1 / scale_sim2real`` to get the simulator's metres, since
         ``cam_maniskill2gs`` scales camera translations by ``scale_sim2real`` (gs_world_wrapper.py:298).  With the default
-        ``()`` nothing changes: no buffer, no launch, :attr:`maps` is None."""
+        ``()`` nothing changes: no buffer, no launch, :attr:`maps` is None.
+        ``pointcloud``: a :class:`gsworld_amd.pointcloud.PointCloudSpec` -- every step then also writes the point cloud of
+        each environment's cameras into :attr:`pointcloud`, ``{"xyzw": (E,N,4) float32, "rgb": (E,N,3) uint8,
+        "segmentation": (E,N,1) int16, "count": (E,) int32}`` (N: every pixel of every camera, or the spec's
+        ``num_points``), loop-owned buffers overwritten by the next step like :attr:`frames`.  It is made from this step's
+        depth / label maps (rendered into private buffers where ``maps`` does not ask for them: :attr:`maps` keeps what
+        ``maps`` asked for), frames and device-resident camera matrices, behind the maps on the same stream (include/gsr.h
+        ``gsr_render_pointcloud``).  Labels are the model's semantics (as for segmentation maps).  With the default None
+        nothing changes: no buffer, no launch, :attr:`pointcloud` is None."""
         maps = tuple(maps or ())
         if any(m not in MAP_KINDS for m in maps) or len(set(maps)) != len(maps):
             raise ValueError(f"maps must be a subset of {MAP_KINDS}, got {maps!r}")
+        if pointcloud is not None:
+            from .pointcloud import PointCloudSpec
+
+            if not isinstance(pointcloud, PointCloudSpec):
+                raise ValueError("pointcloud must be None or a gsworld_amd.pointcloud.PointCloudSpec")
+            pointcloud.validated()
+            if int(num_envs) * len(cameras) > _lib.PC_MAX_VIEWS:
+                raise ValueError(f"pointcloud: at most {_lib.PC_MAX_VIEWS} (environment, camera) views per loop")
         self.device = torch.device(device)
         dev = self.device
         self.num_envs = int(num_envs)
@@ -152,9 +168,11 @@ class ClosedLoopRenderer:
             self.perm = L.perm  # (position in the loop's arrays -> number in the caller's model)
         self._semantics = semantics
         self.map_kinds = tuple(m for m in MAP_KINDS if m in maps)
+        # (what the maps pass writes: the kinds asked for, and both when a point cloud is made from them)
+        self._map_kinds_run = MAP_KINDS if pointcloud is not None else self.map_kinds
         self.depth_scale = float(depth_scale)
         # (the labels of the loop's own arrays -- the permuted copy when laid out -- checked once)
-        self._map_labels = check_map_labels(semantics.to(dev)) if "segmentation" in self.map_kinds else None
+        self._map_labels = check_map_labels(semantics.to(dev)) if "segmentation" in self._map_kinds_run else None
         self.op = tf.FusedPartTransform(part_labels, semantics.to(dev), scaled_parts=scaled_parts)
         self.rescaled = len(tuple(scaled_parts)) > 0
         if self.num_envs > 1:
@@ -177,8 +195,10 @@ class ClosedLoopRenderer:
         self.frames = {n: torch.zeros((self.num_envs, c.image_height, c.image_width, 3), dtype=torch.uint8, device=dev)
                        for n, c in zip(self.names, self.cameras)}
         dts = {"segmentation": torch.int16, "depth": torch.float32}
-        self.maps = {n: {m: torch.zeros((self.num_envs, c.image_height, c.image_width, 1), dtype=dts[m], device=dev)
-                         for m in self.map_kinds} for n, c in zip(self.names, self.cameras)} if self.map_kinds else None
+        self._map_bufs = {n: {m: torch.zeros((self.num_envs, c.image_height, c.image_width, 1), dtype=dts[m], device=dev)
+                              for m in self._map_kinds_run} for n, c in zip(self.names, self.cameras)} \
+            if self._map_kinds_run else None
+        self.maps = {n: {m: b[m] for m in self.map_kinds} for n, b in self._map_bufs.items()} if self.map_kinds else None
         self._maps_pack = None  # (the gsr_render_maps arguments of the lanes, and the state addresses they were built for)
         self.bg = torch.zeros(3, device=dev) if background is None else background.to(dev, torch.float32)
         # the loop never differentiates a frame: inference frames (GsrSettings.forward_only), no radii array
@@ -252,6 +272,17 @@ class ClosedLoopRenderer:
             cams_dev.append(ViewParams(cam.image_width, cam.image_height, cam.FoVx, cam.FoVy, *dv[n]))
         self.cameras = cams_dev
         self._stage.copy_(self._host)
+        # the point cloud's call, packed once: every buffer it reads or writes is the loop's own and never moves (the camera
+        # matrices are the device views of the staging vector, rewritten every step before the frames read them)
+        self.pointcloud, self._cloud_pack = None, None
+        if pointcloud is not None:
+            from .pointcloud import prepare
+
+            cams = dict(zip(self.names, self.cameras))
+            self._cloud_pack = prepare({n: b["depth"] for n, b in self._map_bufs.items()},
+                                       {n: b["segmentation"] for n, b in self._map_bufs.items()}, self.frames, cams,
+                                       pointcloud, self.depth_scale, device=dev)
+            self.pointcloud = self._cloud_pack[1]
         # device-resident pose buffers: what a GPU simulator hands over (ManiSkill link poses are device tensors)
         self.matrices, self.scales = dv["matrices"], dv["scales"]
         # The 17-float pose table(s) the frames read (fuse_transform) live in one persistent buffer and are packed WHERE THE
@@ -358,8 +389,9 @@ class ClosedLoopRenderer:
 
     def _run_maps(self):
         """The step's segmentation / depth maps (``maps``), behind its frames on the current stream: one ``gsr_render_maps``
-        call over every lane (capturable).  The argument pack is kept while no lane's state buffer moves."""
-        if self.maps is None:
+        call over every lane (capturable), then the point cloud from them (``pointcloud``).  The argument pack is kept while
+        no lane's state buffer moves."""
+        if self._map_bufs is None:
             return
         lanes = self.multi.lanes
         key = tuple(l._map_key() for l in lanes)
@@ -368,7 +400,7 @@ class ClosedLoopRenderer:
             frames = []
             for k, lane in enumerate(lanes):
                 e, name = k // C, self.names[k % C]
-                m = self.maps[name]
+                m = self._map_bufs[name]
                 seg, dep = m.get("segmentation"), m.get("depth")
                 f, _, _ = lane._map_frame(self._map_labels if seg is not None else None, self.depth_scale,
                                           seg[e].view(seg.shape[1], seg.shape[2]) if seg is not None else None,
@@ -378,6 +410,8 @@ class ClosedLoopRenderer:
                 frames.append(f)
             self._maps_pack = (key, _C.pack_maps(frames))
         _C.run_maps(self._maps_pack[1], self.device)
+        if self._cloud_pack is not None:
+            _C.run_pointcloud(self._cloud_pack[0], self.device)
 
     def _flush(self):
         """Host-side changes since the last flush go up in as few copies as possible: one contiguous run of the staging
@@ -787,6 +821,8 @@ class PipelinedClosedLoop:
             raise ValueError("depth must be >= 1")
         if kw.get("maps"):
             raise ValueError("PipelinedClosedLoop does not render segmentation / depth maps: use ClosedLoopRenderer(maps=...)")
+        if kw.get("pointcloud") is not None:
+            raise ValueError("PipelinedClosedLoop does not make point clouds: use ClosedLoopRenderer(pointcloud=...)")
         first = ClosedLoopRenderer(raw, part_labels, cameras, **kw)
         self.loops = [first] + [ClosedLoopRenderer(raw, part_labels, cameras, share_model_of=first, **kw)
                                 for _ in range(depth - 1)]

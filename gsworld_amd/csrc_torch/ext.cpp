@@ -18,6 +18,7 @@
 
 #include <cstring>
 #include <tuple>
+#include <vector>
 
 #include "../../include/gsr.h"
 
@@ -384,6 +385,68 @@ void render_maps(int64_t device_index, const py::list &frames) {
     TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
 }
 
+// ---- point clouds of rendered frames (gsworld_amd._C.pack_pointcloud / run_pointcloud) ---------------------------------
+// Built once from (E, C, views, out_from_scene, crop, crop_lo, crop_hi, exclude, mode, K, fps_candidates, out_xyzw,
+// out_rgb, out_segmentation, out_count, workspace, workspace_bytes) -- views: E*C tuples (width, height, tanfovx,
+// tanfovy, viewmatrix, depth, depth_scale, label, rgb8), buffers as device addresses (0 = NULL), as the ctypes path
+// passes them -- and run step after step while no buffer moves.
+struct CloudPack {
+    GsrCloudSpec spec;
+    std::vector<GsrCloudView> views;
+
+    explicit CloudPack(const py::tuple &t) {
+        TORCH_CHECK(t.size() == 17, "CloudPack: 17 values expected, got ", t.size());
+        auto P = [](const py::handle &h) { return reinterpret_cast<void *>((uintptr_t)h.cast<int64_t>()); };
+        std::memset(&spec, 0, sizeof(spec));
+        spec.struct_size = (int32_t)sizeof(GsrCloudSpec);
+        spec.E = t[0].cast<int32_t>();
+        spec.C = t[1].cast<int32_t>();
+        const py::list vl = t[2].cast<py::list>();
+        views.resize(vl.size());
+        for (size_t k = 0; k < vl.size(); k++) {
+            const py::tuple v = vl[k].cast<py::tuple>();
+            TORCH_CHECK(v.size() == 9, "CloudPack: a view is a tuple of 9 values, got ", v.size());
+            GsrCloudView &x = views[k];
+            std::memset(&x, 0, sizeof(x));
+            x.width = v[0].cast<int32_t>();
+            x.height = v[1].cast<int32_t>();
+            x.tanfovx = v[2].cast<float>();
+            x.tanfovy = v[3].cast<float>();
+            x.viewmatrix = static_cast<const float *>(P(v[4]));
+            x.depth = static_cast<const float *>(P(v[5]));
+            x.depth_scale = v[6].cast<float>();
+            x.label = static_cast<const int16_t *>(P(v[7]));
+            x.rgb8 = static_cast<const uint8_t *>(P(v[8]));
+        }
+        spec.views = views.data();
+        const py::list A = t[3].cast<py::list>(), lo = t[5].cast<py::list>(), hi = t[6].cast<py::list>();
+        TORCH_CHECK(A.size() == 12 && lo.size() == 3 && hi.size() == 3, "CloudPack: out_from_scene 12, crop 3 + 3 values");
+        for (int i = 0; i < 12; i++) spec.out_from_scene[i] = A[i].cast<float>();
+        spec.crop = t[4].cast<int32_t>();
+        for (int i = 0; i < 3; i++) {
+            spec.crop_lo[i] = lo[i].cast<float>();
+            spec.crop_hi[i] = hi[i].cast<float>();
+        }
+        spec.exclude = static_cast<const uint32_t *>(P(t[7]));
+        spec.mode = t[8].cast<int32_t>();
+        spec.K = t[9].cast<int32_t>();
+        spec.fps_candidates = t[10].cast<int32_t>();
+        spec.out_xyzw = static_cast<float *>(P(t[11]));
+        spec.out_rgb = static_cast<uint8_t *>(P(t[12]));
+        spec.out_segmentation = static_cast<int16_t *>(P(t[13]));
+        spec.out_count = static_cast<int32_t *>(P(t[14]));
+        spec.workspace = P(t[15]);
+        spec.workspace_bytes = t[16].cast<int64_t>();
+    }
+
+    void run(int64_t device_index) {
+        const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+        c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+        const int rc = gsr_render_pointcloud(&spec, current_stream(dev));
+        TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+    }
+};
+
 // ---- upstream's three functions ------------------------------------------------------------------------------------
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 rasterize_gaussians(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
@@ -574,5 +637,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("run_staged", &StepPack::run_staged);
     m.def("frame_stats", &frame_stats);
     m.def("render_maps", &render_maps);
+    py::class_<CloudPack>(m, "CloudPack").def(py::init<const py::tuple &>()).def("run", &CloudPack::run);
     m.def("version", []() { return std::string(gsr_version()); });
 }

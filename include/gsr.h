@@ -17,6 +17,9 @@
  *   gsr_render_maps        <->  the segmentation / depth observations (obs_mode rgb+segmentation, rgbd) that the wrapper
  *                               leaves to SAPIEN's meshes (gs_world_wrapper.py:184,196,222 overwrite 'rgb' only): here
  *                               from the splatted scene itself, consistent with the frame
+ *   gsr_render_pointcloud  <->  the point-cloud observation (obs_mode pointcloud) the wrapper also leaves to SAPIEN's
+ *                               meshes, plus the crop / FPS step point-cloud policies run after it: world-frame points
+ *                               from the maps, the frame and the camera, sampled to a fixed size on the device
  *
  * Conventions: plain pointers and sizes only (no torch types); every data pointer is DEVICE memory on the
  * current HIP device unless marked [host]; all inputs are borrowed, contiguous, float32; `stream` is a
@@ -476,6 +479,61 @@ int gsr_pack_rgb8(const float *color, int32_t width, int32_t height, uint8_t *ou
 /* upstream markVisible / checkFrustum: present[i] = p_view.z > near_plane. */
 int gsr_mark_visible(int32_t P, const float *means3D, const float *viewmatrix, float near_plane,
                      uint8_t *present, void *stream);
+
+/*
+ * Point clouds of rendered frames (pointcloud.hip: the full definition, evaluation order included, is its header comment).
+ * Per environment e and camera c, from the depth / label maps of gsr_render_maps, the uint8 frame and the camera: a pixel
+ * with depth > 0 unprojects to p = C2W (xv, yv, zv, 1) (C2W = the inverse of the view matrix, computed once per frame in
+ * binary64), the output point is q = out_from_scene p, and the point is VALID when q lies in the crop box (if any) and its
+ * label is not excluded (if a set is given).  Points are ordered camera by camera, then row-major by pixel.  A valid
+ * point's slot holds xyzw = (q, 1), rgb and its label (-1 without label maps); any other slot xyzw = 0, rgb = 0, label -1.
+ *   GSR_PC_DENSE:  N = sum over cameras of W H slots per environment, one per pixel; count[e] = valid points.
+ *   GSR_PC_STRIDE: K slots; with n valid points and M = min(n, K), slot j < M holds the valid point of rank
+ *                  floor(j n / M) (64-bit integers); count[e] = M.
+ *   GSR_PC_FPS:    candidates as in STRIDE with M = min(n, fps_candidates); farthest-point sampling over them from
+ *                  candidate 0 (squared distance ((dx dx) + (dy dy)) + dz dz in binary32, argmax with ties to the lowest
+ *                  index); min(M, K) picks in pick order; count[e] = min(M, K).
+ * Outputs: out_xyzw (E, N|K, 4) float32, out_rgb (E, N|K, 3) uint8, out_segmentation (E, N|K) int16, out_count (E) int32.
+ * At most four launches on `stream`, no allocation, no synchronisation: the call can be captured into a hipGraph.  The
+ * workspace (device, gsr_pointcloud_workspace bytes) holds per-workgroup counts and the FPS candidates.  Limits (else
+ * GSR_E_INVALID): 1 <= E C <= GSR_PC_MAX_VIEWS; every environment's camera c has environment 0's size; at most
+ * GSR_PC_MAX_VIEW_PIXELS pixels per view; 1 <= K <= GSR_PC_MAX_K; 1 <= fps_candidates <= GSR_PC_MAX_FPS_CANDIDATES; an
+ * exclusion set needs every view's label map.
+ */
+#define GSR_PC_DENSE 0
+#define GSR_PC_STRIDE 1
+#define GSR_PC_FPS 2
+#define GSR_PC_MAX_VIEWS 64
+#define GSR_PC_MAX_K 8192
+#define GSR_PC_MAX_FPS_CANDIDATES 16384
+#define GSR_PC_MAX_VIEW_PIXELS (1 << 24)
+typedef struct GsrCloudView {
+    int32_t width, height;
+    float tanfovx, tanfovy;         /* as the frame was rendered (GsrSettings) */
+    const float *viewmatrix;        /* 16 floats: the frame's GsrInputs.viewmatrix (device-resident, read at run time) */
+    const float *depth;             /* (H,W): gsr_render_maps out_depth */
+    float depth_scale;              /* what that depth map was written with */
+    const int16_t *label;           /* (H,W) gsr_render_maps out_label, or NULL */
+    const uint8_t *rgb8;            /* (H,W,3) the frame, or NULL (rgb 0) */
+} GsrCloudView;
+typedef struct GsrCloudSpec {
+    int32_t struct_size;            /* sizeof(GsrCloudSpec): the library rejects a mismatch (GSR_E_INVALID) */
+    int32_t E, C;
+    const GsrCloudView *views;      /* [host] E * C records, environment-major: view e * C + c */
+    float out_from_scene[12];       /* [host] row-major 3 x 4 affine applied to every scene point */
+    int32_t crop;                   /* 1: keep points with crop_lo <= q <= crop_hi (inclusive, per axis) */
+    float crop_lo[3], crop_hi[3];
+    const uint32_t *exclude;        /* 2048 words: bit (uint16)label set = drop the point; or NULL */
+    int32_t mode, K, fps_candidates;
+    float *out_xyzw;
+    uint8_t *out_rgb;
+    int16_t *out_segmentation;
+    int32_t *out_count;
+    void *workspace;
+    int64_t workspace_bytes;
+} GsrCloudSpec;
+int gsr_pointcloud_workspace(const GsrCloudSpec *spec, int64_t *bytes);
+int gsr_render_pointcloud(const GsrCloudSpec *spec, void *stream);
 
 #ifdef __cplusplus
 }
