@@ -342,6 +342,42 @@ def run_pointcloud(pack, device) -> None:
         check(lib().gsr_render_pointcloud(C.byref(p[0]), _stream(dev)))
 
 
+def pack_cameras(n: int, extrinsic, projection, out, offsets, rigid_sim2real, scale_sim2real, binding: str = "auto"):
+    """The arguments of one ``gsr_cameras_from_extrinsics`` call (include/gsr.h), built once: ``n`` views, device tensors
+    ``extrinsic`` / ``projection`` / ``out`` (float32) and ``offsets`` (int32, 3 per view, or None: packed views), the
+    16 floats of ``rigid_sim2real`` (row-major) and ``scale_sim2real``.  The tensors must outlive the pack.  ``binding``:
+    "auto" (the compiled one when built), "ext" or "ctypes"."""
+    def ptr(t):
+        return int(t.data_ptr()) if t is not None and t.numel() else 0
+
+    vals = (int(n), ptr(extrinsic), ptr(projection), ptr(out), ptr(offsets), [float(x) for x in rigid_sim2real],
+            float(scale_sim2real))
+    use_ext = _ext is not None and hasattr(_ext, "CamPack") if binding == "auto" else binding == "ext"
+    if use_ext:
+        if _ext is None or not hasattr(_ext, "CamPack"):
+            raise RuntimeError("the compiled binding (gsworld_amd._C_ext) with CamPack is not built")
+        return ("ext", _ext.CamPack(vals))
+    cs = _lib.GsrSensorCameras()
+    cs.struct_size = C.sizeof(_lib.GsrSensorCameras)
+    cs.n = vals[0]
+    cs.extrinsic, cs.projection, cs.out, cs.offsets = (v or None for v in vals[1:5])
+    cs.rigid_sim2real[:] = vals[5]
+    cs.scale_sim2real = vals[6]
+    return ("ctypes", cs)
+
+
+def run_cameras(pack, device) -> None:
+    """Enqueues the ``gsr_cameras_from_extrinsics`` call of :func:`pack_cameras` on the current stream of ``device``
+    (capturable)."""
+    kind, p = pack
+    dev = torch.device(device)
+    if kind == "ext":
+        p.run(dev.index if dev.index is not None else torch.cuda.current_device())
+        return
+    with torch.cuda.device(dev):
+        check(lib().gsr_cameras_from_extrinsics(C.byref(p), _stream(dev)))
+
+
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                         prefiltered, antialiasing, debug, sh_rest=None, param_space: int = 0):

@@ -148,6 +148,16 @@ class GsrCloudSpec(C.Structure):
                 ("workspace_bytes", C.c_int64)]
 
 
+CAM_MAX_VIEWS, CAM_RECORD_FLOATS = 4096, 36  # include/gsr.h GSR_CAM_*
+
+
+class GsrSensorCameras(C.Structure):
+    """The arguments of ``gsr_cameras_from_extrinsics`` (include/gsr.h): camera records from simulator extrinsics."""
+    _fields_ = [("struct_size", C.c_int32), ("n", C.c_int32), ("extrinsic", C.c_void_p), ("projection", C.c_void_p),
+                ("out", C.c_void_p), ("offsets", C.c_void_p), ("rigid_sim2real", C.c_double * 16),
+                ("scale_sim2real", C.c_double)]
+
+
 class GsrProfile(C.Structure):
     _fields_ = [("frames", C.c_int32), ("stage_ms", C.c_double * 5)]
 
@@ -222,6 +232,8 @@ def lib() -> C.CDLL:
     L.gsr_render_pointcloud.argtypes = [C.POINTER(GsrCloudSpec), C.c_void_p]
     L.gsr_pointcloud_workspace.restype = C.c_int
     L.gsr_pointcloud_workspace.argtypes = [C.POINTER(GsrCloudSpec), C.POINTER(C.c_int64)]
+    L.gsr_cameras_from_extrinsics.restype = C.c_int
+    L.gsr_cameras_from_extrinsics.argtypes = [C.POINTER(GsrSensorCameras), C.c_void_p]
     L.gsr_profile_enable.restype = C.c_int
     L.gsr_profile_enable.argtypes = [C.c_int]
     L.gsr_profile_collect.restype = C.c_int

@@ -4,7 +4,9 @@ Restates (a) the camera conversion GSWorld performs per frame,
 ``GSWorldWrapper.cam_maniskill2gs`` (/root/reference/gsworld/mani_skill/utils/wrappers/gs_world_wrapper.py:277-325),
 and (b) the view/projection construction of the un-vendored 3DGS python layer it feeds
 (``utils/graphics_utils.py`` getWorld2View2 / getProjectionMatrix and ``scene/cameras.py`` Camera;
-SURVEY.md Appendix B.1).  Pure numpy/torch host code: runs once per camera, not on the hot path.
+SURVEY.md Appendix B.1).  Pure numpy/torch host code: runs once per camera, not on the hot path.  The per-step conversion of a simulator's
+device-resident sensor poses is ``gsr_cameras_from_extrinsics`` (csrc/camera.hip), which ``ClosedLoopRenderer.
+set_extrinsics`` runs on the GPU; :func:`sensor_projection` is the constant it reads per camera.
 """
 from __future__ import annotations
 
@@ -146,3 +148,38 @@ def look_at_view(eye, target, up, fov_x: float, fov_y: float, width: int, height
     w2c_R = c2w_R.T
     T = -w2c_R @ eye
     return view_params(w2c_R.T, T, fov_x, fov_y, width, height)
+
+
+def sensor_projection(FoVx: float, FoVy: float) -> torch.Tensor:
+    """The float32 (4,4) ``getProjectionMatrix(0.01, 100, FoVx, FoVy)^T`` a camera of this field of view multiplies its
+    world_view by (``full_proj_transform = world_view @ this``); ``gsr_cameras_from_extrinsics`` reads it per view."""
+    return get_projection_matrix(ZNEAR, ZFAR, FoVx, FoVy).transpose(0, 1).contiguous()
+
+
+def view_params_from_record(record, width: int, height: int, FoVx: float, FoVy: float) -> ViewParams:
+    """A camera from a 36-float record -- world_view (16) | full_proj (16) | centre (3) | pad -- as
+    ``gsr_cameras_from_extrinsics`` writes it and the closed loop's staging vector holds it (host float32 copies)."""
+    r = torch.as_tensor(record).detach().to("cpu", torch.float32).reshape(-1)
+    return ViewParams(int(width), int(height), float(FoVx), float(FoVy), r[:16].view(4, 4).clone(),
+                      r[16:32].view(4, 4).clone(), r[32:35].clone())
+
+
+def cameras_from_sensor_params(params: dict, sizes: dict, rigid_sim2real, scale_sim2real) -> dict:
+    """``{name: [E ViewParams]}`` from ManiSkill's ``base_env.get_sensor_params()`` layout -- ``params[name]
+    ["extrinsic_cv"]`` (E,3,4) and ``["intrinsic_cv"]`` (E,3,3) -- with :func:`cam_maniskill2gs` per environment, for the
+    cameras named in ``sizes`` (``{name: (width, height)}``).  What ``ClosedLoopRenderer(per_env_cameras=True)`` is built
+    from: each environment's own pose and field of view (the reference's wrapper takes environment 0's for all)."""
+    rigid = torch.as_tensor(rigid_sim2real).detach().cpu()
+    out = {}
+    for name, (w, h) in sizes.items():
+        p = params[name]
+        ext = torch.as_tensor(p["extrinsic_cv"]).detach().cpu()
+        K = torch.as_tensor(p["intrinsic_cv"]).detach().cpu()
+        if ext.dim() == 2:
+            ext = ext.unsqueeze(0)
+        if K.dim() == 2:
+            K = K.unsqueeze(0).expand(ext.shape[0], 3, 3)
+        if ext.dim() != 3 or tuple(ext.shape[1:]) != (3, 4) or tuple(K.shape) != (ext.shape[0], 3, 3):
+            raise ValueError(f"camera {name!r}: extrinsic_cv must be (E,3,4) and intrinsic_cv (E,3,3)")
+        out[name] = [cam_maniskill2gs(ext[e], K[e], int(w), int(h), rigid, scale_sim2real) for e in range(ext.shape[0])]
+    return out

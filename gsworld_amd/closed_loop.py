@@ -42,6 +42,52 @@ def _to_mirror(dst: torch.Tensor, dst_np, src: torch.Tensor) -> None:
 MAP_KINDS = ("segmentation", "depth")
 
 
+def _camera_list(name, value, num_envs: int, per_env: bool) -> list:
+    """A camera argument as the list of ViewParams its environments see: one for all (``per_env`` False, or a single
+    ViewParams), or E of one image size (``ValueError`` otherwise)."""
+    from .camera import ViewParams
+
+    if isinstance(value, ViewParams) or not isinstance(value, (list, tuple)):
+        return [value] * (num_envs if per_env else 1)
+    if not per_env:
+        raise ValueError(f"camera {name!r}: one ViewParams per camera (a list per environment needs per_env_cameras=True)")
+    if len(value) != num_envs:
+        raise ValueError(f"camera {name!r}: {len(value)} ViewParams for {num_envs} environments")
+    if len({(int(c.image_width), int(c.image_height)) for c in value}) != 1:
+        raise ValueError(f"camera {name!r}: every environment's camera must have the same image size")
+    return list(value)
+
+
+def check_sim2real(sim2real):
+    """``(rigid_sim2real (4,4), scale_sim2real)`` -> (16 row-major floats, scale) as ``gsr_cameras_from_extrinsics`` takes
+    them; ``ValueError`` for anything else."""
+    if not isinstance(sim2real, (list, tuple)) or len(sim2real) != 2:
+        raise ValueError("sim2real must be (rigid_sim2real (4,4), scale_sim2real)")
+    R = sim2real[0].detach().cpu().numpy() if isinstance(sim2real[0], torch.Tensor) else np.asarray(sim2real[0])
+    s = sim2real[1].detach().cpu().numpy() if isinstance(sim2real[1], torch.Tensor) else np.asarray(sim2real[1])
+    R, s = R.astype(np.float64), s.astype(np.float64)
+    if R.shape != (4, 4) or not np.all(np.isfinite(R)) or s.size != 1 or not np.isfinite(s.reshape(-1)[0]) or \
+            float(s.reshape(-1)[0]) == 0.0:
+        raise ValueError("sim2real must be (rigid_sim2real (4,4) finite, scale_sim2real finite and non-zero)")
+    return [float(x) for x in R.reshape(-1)], float(s.reshape(-1)[0])
+
+
+def check_extrinsics(name, value, num_envs: int, per_env: bool, has_sim2real: bool) -> torch.Tensor:
+    """An ``extrinsic_cv`` argument of :meth:`ClosedLoopRenderer.set_extrinsics` as a float32 tensor of the shape the loop
+    stages, ``(E,3,4)`` (per-environment cameras) or ``(1,3,4)``; ``ValueError`` for a wrong shape or a loop built without
+    ``sim2real``."""
+    if not has_sim2real:
+        raise ValueError("extrinsics need sim2real=(rigid_sim2real, scale_sim2real) at construction")
+    t = value if isinstance(value, torch.Tensor) else torch.as_tensor(np.asarray(value))
+    want = (num_envs, 3, 4) if per_env else (1, 3, 4)
+    if not (tuple(t.shape) == want or (not per_env and tuple(t.shape) == (3, 4))):
+        raise ValueError(f"extrinsics of camera {name!r}: expected shape {want}" + ("" if per_env else " or (3, 4)") +
+                         f", got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    return t.reshape(want)
+
+
 def check_map_labels(labels: torch.Tensor) -> torch.Tensor:
     """The per-Gaussian semantic labels of a segmentation map as ``gsr_render_maps`` reads them: (P,) float32, dense, on the
     labels' device.  Every label must be an integral value inside int16 (the map stores ``(int16)(int)label``); anything else
@@ -57,7 +103,7 @@ class ClosedLoopRenderer:
                  background=None, fuse_transform: bool = True, growth: float = 2.0, bound_capacity="auto",
                  layout: bool = True, min_capacity: int | None = None, share_model_of=None, batched: bool = True,
                  keep_float: bool = False, block_cache: bool = True, tile_reuse: bool = True, maps=(),
-                 depth_scale: float = 1.0, pointcloud=None):
+                 depth_scale: float = 1.0, pointcloud=None, per_env_cameras: bool = False, sim2real=None):
         """``raw``: :class:`gsworld_amd.scenes.RawGaussians` (or any object with the same raw parameter tensors, e.g. a
         merged semantic model's ``_xyz`` ... under those names); ``part_labels``: part name -> semantic label(s), in
         the order the pose matrices will arrive; ``cameras``: name -> :class:`gsworld_amd.camera.ViewParams`;
@@ -110,8 +156,20 @@ class ClosedLoopRenderer:
         depth / label maps (rendered into private buffers where ``maps`` does not ask for them: :attr:`maps` keeps what
         ``maps`` asked for), frames and device-resident camera matrices, behind the maps on the same stream (include/gsr.h
         ``gsr_render_pointcloud``).  Labels are the model's semantics (as for segmentation maps).  With the default None
-        nothing changes: no buffer, no launch, :attr:`pointcloud` is None."""
+        nothing changes: no buffer, no launch, :attr:`pointcloud` is None.
+        ``per_env_cameras``: every camera has one record per environment -- ``cameras[name]`` is a ViewParams (every
+        environment starts there) or a sequence of ``num_envs`` of one image size (field of view may differ per
+        environment; it is fixed at construction).  :meth:`set_cameras` / :meth:`step` take the same two forms, and
+        :attr:`env_cameras` ``[name][e]`` are the device-resident cameras environment e's frames read.  False (default):
+        one camera per name for every environment, as the reference's wrapper does (environment 0's sensor pose).
+        ``sim2real``: ``(rigid_sim2real (4,4), scale_sim2real)`` of the wrapper -- needed to hand over the simulator's
+        ``extrinsic_cv`` directly (:meth:`set_extrinsics`): the camera records are then computed on the device in the
+        step itself (include/gsr.h ``gsr_cameras_from_extrinsics``)."""
         maps = tuple(maps or ())
+        self.per_env_cameras = bool(per_env_cameras)
+        E0 = int(num_envs)
+        cam_lists = {n: _camera_list(n, v, E0, self.per_env_cameras) for n, v in cameras.items()}
+        self._sim2real = check_sim2real(sim2real) if sim2real is not None else None
         if any(m not in MAP_KINDS for m in maps) or len(set(maps)) != len(maps):
             raise ValueError(f"maps must be a subset of {MAP_KINDS}, got {maps!r}")
         if pointcloud is not None:
@@ -126,7 +184,7 @@ class ClosedLoopRenderer:
         dev = self.device
         self.num_envs = int(num_envs)
         self.names = list(cameras.keys())
-        self._given_cameras = [cameras[n] for n in self.names]
+        self._given_cameras = [cam_lists[n][0] for n in self.names]
         self.cameras = self._given_cameras  # (image sizes; replaced by device-resident copies once the staging vector exists)
         g = lambda a, b: getattr(raw, a) if hasattr(raw, a) else getattr(raw, b)  # noqa: E731
         other = share_model_of
@@ -236,9 +294,18 @@ class ClosedLoopRenderer:
         nm, ns = self.num_envs * self.K * 16, self.num_envs * self.K
         self._seg = {"poses": (0, nm + (ns + 3) // 4 * 4)}
         off = self._seg["poses"][1]
+        # (per_env_cameras: E records per camera, environment e's at +36 e)
+        self._ecam = self.num_envs if self.per_env_cameras else 1
         for n in self.names:
-            self._seg[n] = (off, off + 36)  # world_view (16) | full_proj (16) | centre (3) + pad
-            off += 36
+            self._seg[n] = (off, off + 36 * self._ecam)  # world_view (16) | full_proj (16) | centre (3) + pad
+            off += 36 * self._ecam
+        # with sim2real: the simulator's extrinsics (12 floats per record) travel in the staging vector too, and
+        # gsr_cameras_from_extrinsics turns them into the records above on the device, inside the step
+        self._ext_segs = ["ext:" + n for n in self.names] if self._sim2real is not None else []
+        for n in self._ext_segs:
+            self._seg[n] = (off, off + 12 * self._ecam)
+            off += 12 * self._ecam
+        self._seg_order = ["poses"] + self.names + self._ext_segs
         self._stage = torch.zeros(off, device=dev)
         self._host = torch.zeros(off)
         pin = dev.type == "cuda" and torch.cuda.is_available()
@@ -251,34 +318,52 @@ class ClosedLoopRenderer:
             v = {"matrices": buf[:nm].view(*lead, 4, 4), "scales": buf[nm:nm + ns].view(lead)}
             for n in self.names:
                 o = self._seg[n][0]
-                v[n] = (buf[o:o + 16].view(4, 4), buf[o + 16:o + 32].view(4, 4), buf[o + 32:o + 35])
+                v[n] = [(buf[r:r + 16].view(4, 4), buf[r + 16:r + 32].view(4, 4), buf[r + 32:r + 35])
+                        for r in range(o, o + 36 * self._ecam, 36)]
+            for n in self._ext_segs:
+                o = self._seg[n][0]
+                v[n] = buf[o:o + 12 * self._ecam].view(self._ecam, 3, 4)
             return v
 
         self._hv, dv = views(self._host), views(self._stage)
         # (the same host memory as numpy arrays: what a step writes into the mirror and the ring are a dozen copies of a
         #  few hundred bytes, ~0.4 us each through numpy against 1.5-2 us through a torch op -- with the policy in the loop
         #  the host's share of a step is on the critical path: round 6, tools/host_step_profile.py)
-        self._hv_np = {k: (tuple(x.numpy() for x in v) if isinstance(v, tuple) else v.numpy()) for k, v in self._hv.items()}
+        self._hv_np = {k: ([tuple(x.numpy() for x in r) for r in v] if isinstance(v, list) else v.numpy())
+                       for k, v in self._hv.items()}
         self._host_np = self._host.numpy()
         self._ring_np = [r.numpy() for r in self._ring]
         self._hv["matrices"].copy_(torch.eye(4).expand(*lead, 4, 4))
         self._hv["scales"].fill_(1.0)
         from .camera import ViewParams
 
-        cams_dev = []
-        for n, cam in zip(self.names, self._given_cameras):
-            for dst, src in zip(self._hv[n], (cam.world_view_transform, cam.full_proj_transform, cam.camera_center)):
-                dst.copy_(src.detach().to("cpu", torch.float32))
-            cams_dev.append(ViewParams(cam.image_width, cam.image_height, cam.FoVx, cam.FoVy, *dv[n]))
-        self.cameras = cams_dev
+        self.env_cameras = {}
+        for n in self.names:
+            recs = []
+            for j, cam in enumerate(cam_lists[n]):
+                for dst, src in zip(self._hv[n][j], (cam.world_view_transform, cam.full_proj_transform, cam.camera_center)):
+                    dst.copy_(src.detach().to("cpu", torch.float32))
+                recs.append(ViewParams(cam.image_width, cam.image_height, cam.FoVx, cam.FoVy, *dv[n][j]))
+            self.env_cameras[n] = recs if self.per_env_cameras else recs * self.num_envs
+        self.cameras = [self.env_cameras[n][0] for n in self.names]
         self._stage.copy_(self._host)
+        # extrinsic-fed cameras (set_extrinsics): their records are written by gsr_cameras_from_extrinsics from the staged
+        # extrinsics at the start of every step; the call's pack is rebuilt when the set of such cameras changes
+        self._dv = dv
+        self._ext_names, self._cams_pack, self._ext_changed = [], None, False
+        if self._sim2real is not None:
+            from .camera import sensor_projection
+
+            # (one float32 projection per record, fixed for the loop's lifetime: camera by camera, environment e at +16 e)
+            self._proj = torch.stack([sensor_projection(c.FoVx, c.FoVy) for n in self.names
+                                      for c in self.env_cameras[n][:self._ecam]]).to(dev).contiguous()
         # the point cloud's call, packed once: every buffer it reads or writes is the loop's own and never moves (the camera
         # matrices are the device views of the staging vector, rewritten every step before the frames read them)
         self.pointcloud, self._cloud_pack = None, None
         if pointcloud is not None:
             from .pointcloud import prepare
 
-            cams = dict(zip(self.names, self.cameras))
+            cams = dict(self.env_cameras) if self.per_env_cameras else dict(zip(self.names, self.cameras))
             self._cloud_pack = prepare({n: b["depth"] for n, b in self._map_bufs.items()},
                                        {n: b["segmentation"] for n, b in self._map_bufs.items()}, self.frames, cams,
                                        pointcloud, self.depth_scale, device=dev)
@@ -324,7 +409,8 @@ class ClosedLoopRenderer:
         self._sync_fn = getattr(_C._ext, "sync_current_stream", None) if (_C._ext is not None and dev.type == "cuda") else None
         self._dev_index = dev.index if dev.index is not None else (torch.cuda.current_device() if dev.type == "cuda" else 0)
         self._mat_shape = tuple(self.matrices.shape)
-        self._cam_meta = {n: (self._seg[n][0], c.image_width, c.image_height, c.FoVx, c.FoVy)
+        self._cam_meta = {n: (self._seg[n][0], c.image_width, c.image_height,
+                              [(v.FoVx, v.FoVy) for v in self.env_cameras[n][:self._ecam]])
                           for n, c in zip(self.names, self.cameras)}
         self.eager_when_waited = False  # ... step(ensure=True) too (A/B: the graph's one submission against eleven launches)
         self.image_size = (H, W)
@@ -347,6 +433,7 @@ class ClosedLoopRenderer:
         E, C = self.num_envs, len(self.cameras)
         if not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
             self._flush()
+        self._run_cameras()
         if self.fuse_transform:
             # (the pose table was packed when the poses arrived: _flush / set_poses)
             parts = self.op.parts_of_table(self._table) if self._table is not None else \
@@ -354,7 +441,7 @@ class ClosedLoopRenderer:
             views, outs, per_lane = [], [], []
             for e in range(E):
                 for c in range(C):
-                    views.append(self.cameras[c])
+                    views.append(self.env_cameras[self.names[c]][e])
                     outs.append(self.frames[self.names[c]][e])
                     per_lane.append(dict(parts=parts if E == 1 else parts[e]))
             self.multi.render(views, self.xyz, self.opacity, rgb8_out=outs, shs=self.features_dc,
@@ -373,7 +460,7 @@ class ClosedLoopRenderer:
         views, outs = [], []
         for e in range(E):
             for c in range(C):
-                views.append(self.cameras[c])
+                views.append(self.env_cameras[self.names[c]][e])
                 outs.append(self.frames[self.names[c]][e])
         if E == 1:
             self.multi.render(views, xyz, self.opacity, rgb8_out=outs, shs=self.features_dc,
@@ -386,6 +473,35 @@ class ClosedLoopRenderer:
                               shs_rest=self.features_rest, param_space=RAW_SCALES | RAW_ROTATIONS, bg=self.bg,
                               per_lane=per_lane)
         self._run_maps()
+
+    def _run_cameras(self):
+        """The records of the extrinsic-fed cameras from their staged extrinsics (``gsr_cameras_from_extrinsics``, one
+        launch on the current stream, capturable) -- behind the step's staging, ahead of its frames."""
+        if self._ext_names:
+            _C.run_cameras(self._cameras_pack(), self.device)
+
+    def _cameras_pack(self):
+        """The ``gsr_cameras_from_extrinsics`` arguments of the current set of extrinsic-fed cameras (built when the set
+        changes, outside any capture: set_extrinsics / set_cameras): views environment-major, every record read and
+        written in place in the staging vector."""
+        if self._cams_pack is None:
+            offs = []
+            for e in range(self._ecam):
+                for n in self._ext_names:
+                    c = self.names.index(n)
+                    offs += [self._seg["ext:" + n][0] + 12 * e, 16 * (c * self._ecam + e), self._seg[n][0] + 36 * e]
+            t = torch.tensor(offs, dtype=torch.int32, device=self.device)
+            rigid, scale = self._sim2real
+            self._cams_pack = (_C.pack_cameras(len(offs) // 3, self._stage, self._proj, self._stage, t, rigid, scale), t)
+        return self._cams_pack[0]
+
+    def _ext_set(self, names):
+        """The extrinsic-fed cameras are now ``names``: a new call pack, and a captured step is captured again."""
+        names = [n for n in self.names if n in names]
+        if names != self._ext_names:
+            self._ext_names, self._cams_pack, self._ext_changed = names, None, True
+            if names:
+                self._cameras_pack()
 
     def _run_maps(self):
         """The step's segmentation / depth maps (``maps``), behind its frames on the current stream: one ``gsr_render_maps``
@@ -420,7 +536,7 @@ class ClosedLoopRenderer:
         ring, so the caller may overwrite its tensors -- and this object its mirror -- right away."""
         if not self._dirty:
             return
-        order = ["poses"] + self.names
+        order = self._seg_order
         runs, cur = [], None
         first = min(order.index(n) for n in self._dirty)
         last = max(order.index(n) for n in self._dirty)
@@ -472,7 +588,7 @@ class ClosedLoopRenderer:
         self._dirty.clear()
         return k
 
-    def _stage_host_values_fast(self, matrices, scales, cameras):
+    def _stage_host_values_fast(self, matrices, scales, cameras, extrinsics=None):
         """This step's poses and cameras -- plain host float32 tensors, the usual case -- into the host mirror and the next
         ring slot in ONE call into the compiled binding (csrc_torch/ext.cpp stage_host_values) instead of set_poses +
         set_cameras + the ring copy: 13 -> ~4 us of host work that sits on the critical path of a waited-for step.
@@ -486,17 +602,30 @@ class ClosedLoopRenderer:
             if scales is not None:
                 segs.append((self.num_envs * self.K * 16, scales))
         if cameras:
-            for name, cam in cameras.items():
+            for name, cams in cameras.items():
                 meta = self._cam_meta.get(name)
-                if meta is None:
-                    return None  # (set_cameras raises the KeyError)
-                o, w, h, fx, fy = meta
-                if cam.image_width != w or cam.image_height != h or abs(cam.FoVx - fx) > 1e-9 or abs(cam.FoVy - fy) > 1e-9:
-                    return None  # (set_cameras raises the ValueError)
-                wv, fp, cc = cam.world_view_transform, cam.full_proj_transform, cam.camera_center
-                if wv.numel() != 16 or fp.numel() != 16 or cc.numel() != 3:
-                    return None
-                segs += [(o, wv), (o + 16, fp), (o + 32, cc)]
+                if meta is None or name in self._ext_names:
+                    return None  # (set_cameras raises the KeyError / takes the camera off the extrinsic-fed set)
+                o, w, h, fovs = meta
+                if isinstance(cams, (list, tuple)):
+                    if len(cams) != len(fovs):
+                        return None
+                else:
+                    cams = [cams] * len(fovs)
+                for j, (cam, (fx, fy)) in enumerate(zip(cams, fovs)):
+                    if cam.image_width != w or cam.image_height != h or abs(cam.FoVx - fx) > 1e-9 or \
+                            abs(cam.FoVy - fy) > 1e-9:
+                        return None  # (set_cameras raises the ValueError)
+                    wv, fp, cc = cam.world_view_transform, cam.full_proj_transform, cam.camera_center
+                    if wv.numel() != 16 or fp.numel() != 16 or cc.numel() != 3:
+                        return None
+                    r = o + 36 * j
+                    segs += [(r, wv), (r + 16, fp), (r + 32, cc)]
+        if extrinsics:
+            for name, ext in extrinsics.items():
+                if name not in self._ext_names or not isinstance(ext, torch.Tensor) or ext.numel() != 12 * self._ecam:
+                    return None  # (set_extrinsics adds the camera or raises)
+                segs.append((self._seg["ext:" + name][0], ext))
         # (the slot is taken before the write: its last reader has finished by then)
         ring_k, ring_ev, waited = self._ring_k, list(self._ring_ev), self._ring_waited
         k = self._slot_acquire()
@@ -537,27 +666,60 @@ class ClosedLoopRenderer:
         (gs_world_wrapper.py:238 ``self.gs_cam = self.cam_maniskill2gs(self.base_env.get_sensor_params(), ...)``), which
         is how a wrist-mounted camera follows the arm.  The matrices are copied INTO the device tensors the (possibly
         captured) step reads; image size and field of view are part of the launch and must not change."""
+        lists = {}
         for name, cam in cameras.items():
             if name not in self.names:
                 raise KeyError(f"unknown camera {name!r} (known: {self.names})")
-            mine = self.cameras[self.names.index(name)]
-            if (cam.image_width, cam.image_height) != (mine.image_width, mine.image_height) or \
-                    abs(cam.FoVx - mine.FoVx) > 1e-9 or abs(cam.FoVy - mine.FoVy) > 1e-9:
-                raise ValueError(f"camera {name!r}: image size / field of view are fixed at construction")
-            src = (cam.world_view_transform, cam.full_proj_transform, cam.camera_center)
-            if any(t.is_cuda for t in src):
+            lists[name] = _camera_list(name, cam, self.num_envs, self.per_env_cameras)
+            for cam, mine in zip(lists[name], self.env_cameras[name]):
+                if (cam.image_width, cam.image_height) != (mine.image_width, mine.image_height) or \
+                        abs(cam.FoVx - mine.FoVx) > 1e-9 or abs(cam.FoVy - mine.FoVy) > 1e-9:
+                    raise ValueError(f"camera {name!r}: image size / field of view are fixed at construction")
+        for name, cams in lists.items():
+            srcs = [(c.world_view_transform, c.full_proj_transform, c.camera_center) for c in cams]
+            if any(t.is_cuda for src in srcs for t in src):
                 self._flush()
-                for dst, t in zip((mine.world_view_transform, mine.full_proj_transform, mine.camera_center), src):
-                    dst.copy_(t.to(torch.float32), non_blocking=True)
+                for mine, src in zip(self.env_cameras[name], srcs):
+                    for dst, t in zip((mine.world_view_transform, mine.full_proj_transform, mine.camera_center), src):
+                        dst.copy_(t.to(torch.float32), non_blocking=True)
                 self._stale.add(name)
             else:
-                for dst, dst_np, t in zip(self._hv[name], self._hv_np[name], src):
-                    _to_mirror(dst, dst_np, t)
+                for j, src in enumerate(srcs):
+                    for dst, dst_np, t in zip(self._hv[name][j], self._hv_np[name][j], src):
+                        _to_mirror(dst, dst_np, t)
                 self._dirty.add(name)
+        if any(n in self._ext_names for n in lists):
+            self._ext_set([n for n in self._ext_names if n not in lists])
+
+    def set_extrinsics(self, extrinsics: dict):
+        """This step's camera poses as the simulator holds them: ``{name: extrinsic_cv}`` (OpenCV world -> camera, float32;
+        ManiSkill ``base_env.get_sensor_params()[name]["extrinsic_cv"]``), ``(E,3,4)`` with ``per_env_cameras`` or
+        ``(3,4)`` / ``(1,3,4)`` without, on the host or the device.  Needs ``sim2real`` at construction.  Host values travel
+        with the step's other host values; device values are copied device to device into the loop's buffer.  The step then
+        computes the cameras' records on the GPU (include/gsr.h ``gsr_cameras_from_extrinsics``: what ``cam_maniskill2gs``
+        computes on the host, with each camera's field of view as given at construction) before its frames read them.  A
+        camera stays extrinsic-fed until :meth:`set_cameras` hands it a ViewParams again."""
+        checked = {}
+        for name, ext in extrinsics.items():
+            if name not in self.names:
+                raise KeyError(f"unknown camera {name!r} (known: {self.names})")
+            checked[name] = check_extrinsics(name, ext, self.num_envs, self.per_env_cameras, self._sim2real is not None)
+        for name, t in checked.items():
+            seg = "ext:" + name
+            if t.is_cuda:
+                self._flush()
+                self._dv[seg].copy_(t, non_blocking=True)
+                self._stale.add(seg)
+            else:
+                _to_mirror(self._hv[seg], self._hv_np[seg], t)
+                self._dirty.add(seg)
+        self._ext_set(self._ext_names + list(checked))
 
     def step(self, matrices: torch.Tensor | None = None, scales: torch.Tensor | None = None,
-             cameras: dict | None = None, ensure: bool = False) -> dict:
+             cameras: dict | None = None, ensure: bool = False, extrinsics: dict | None = None) -> dict:
         """-> {camera name: uint8 (num_envs, H, W, 3)} -- renderer-owned tensors, overwritten by the next step.
+
+        ``cameras``: as :meth:`set_cameras`; ``extrinsics``: as :meth:`set_extrinsics` (this step's simulator sensor poses).
 
         A lane whose instance list is sized from earlier frames (no ``bound_capacity``) can be outgrown by a later frame
         -- an arm swinging past a wrist camera triples the count -- and such a frame shows the background only.  That is
@@ -574,14 +736,19 @@ class ClosedLoopRenderer:
           invalid."""
         pre_k = None
         if self._graphs is not None and not self._stale and self._stage_fn is not None:
-            pre_k = self._stage_host_values_fast(matrices, scales, cameras)  # (None: not plain host tensors -- the general path)
+            # (None: not plain host tensors -- the general path)
+            pre_k = self._stage_host_values_fast(matrices, scales, cameras, extrinsics)
         if pre_k is None:
             if matrices is not None:
                 self.set_poses(matrices, scales)
             if cameras:
                 self.set_cameras(cameras)
-        if self._graphs is not None and self._stale:
-            self.capture()  # (device tensors arrived since the capture: their values must not be staged over)
+            if extrinsics:
+                self.set_extrinsics(extrinsics)
+        if (self._graphs is not None and self._stale) or (self._ext_changed and self.captured):
+            # (device tensors arrived since the capture: their values must not be staged over; or the set of extrinsic-fed
+            #  cameras changed: the captured conversion launch converts the old set)
+            self.capture()
         if (not ensure or self.eager_when_waited) and self.eager_when_ahead and self._pack is not None and \
                 self._table is not None and self._ring_dev is not None and not self._stale and \
                 (self._graphs is not None or self._graph is None):
@@ -593,16 +760,21 @@ class ClosedLoopRenderer:
             # against 7.25 k -- and `ensure=True` takes it.
             k = pre_k if pre_k is not None else self._slot_stage()
             pack, caps = self._pack
-            if pack[0] == "pack":
+            if pack[0] == "pack" and (not self._ext_names or self._cameras_pack()[0] == "ext"):
                 # (the staging kernel and the frames' launches in ONE call into the compiled binding: csrc_torch/ext.cpp StepPack)
                 nm, ns = self.num_envs * self.K * 16, self.num_envs * self.K
                 with torch.cuda.device(self.device):
-                    pack[1].run_staged(int(self._stage.numel()), self._ring_dev[k], self._stage.data_ptr(), ns, 0, nm,
-                                       self._table.data_ptr())
+                    if self._ext_names:  # (the camera records of the staged extrinsics between staging and frames)
+                        pack[1].run_staged_cams(int(self._stage.numel()), self._ring_dev[k], self._stage.data_ptr(), ns, 0,
+                                                nm, self._table.data_ptr(), self._cameras_pack()[1])
+                    else:
+                        pack[1].run_staged(int(self._stage.numel()), self._ring_dev[k], self._stage.data_ptr(), ns, 0, nm,
+                                           self._table.data_ptr())
                 for lane, cap in caps:
                     lane._finish(cap)
             else:
                 self._launch_stage(k, int(self._stage.numel()))
+                self._run_cameras()
                 self.multi.rerun(self._pack)
             self._run_maps()
             self._slot_release(k, ensure)
@@ -617,6 +789,7 @@ class ClosedLoopRenderer:
             self._graph.replay()
         elif self._pack is not None and self.fuse_transform and self._table is not None:
             self._flush()
+            self._run_cameras()
             self.multi.rerun(self._pack)  # (the frames' arguments have not changed: device buffers, written by the flush)
             self._run_maps()
         else:
@@ -743,7 +916,7 @@ class ClosedLoopRenderer:
 
     def _flush_all(self):
         """(after staged graphs: the eager path stages what is dirty only -- everything the host holds is, once)"""
-        self._dirty.update(n for n in ["poses"] + self.names if n not in self._stale)
+        self._dirty.update(n for n in self._seg_order if n not in self._stale)
 
     def capture(self):
         """Captures the GPU side of a step into a hipGraph (call after :meth:`reset`).
@@ -757,6 +930,7 @@ class ClosedLoopRenderer:
         frames, and whatever the host still provides goes up in front of each replay."""
         dev = self.device
         self._graph = self._graphs = None
+        self._ext_changed = False
         self._gpu_step()
         self.multi.ensure_valid(self._gpu_step)
         self._pack = self.multi.last_pack if self.fuse_transform and self._table is not None else None
@@ -858,7 +1032,10 @@ class PipelinedClosedLoop:
                 loop.capture()
         torch.cuda.synchronize(self.device)
 
-    def step(self, matrices=None, scales=None, cameras: dict | None = None, wait: bool = True, ensure: bool = False) -> dict:
+    def step(self, matrices=None, scales=None, cameras: dict | None = None, wait: bool = True, ensure: bool = False,
+             extrinsics: dict | None = None) -> dict:
+        """(``per_env_cameras`` / ``sim2real`` go to every loop; ``cameras`` / ``extrinsics`` as
+        :meth:`ClosedLoopRenderer.step`)"""
         i = self._k % len(self.loops)
         self._k += 1
         loop, st = self.loops[i], self.streams[i]
@@ -874,11 +1051,13 @@ class PipelinedClosedLoop:
             st.wait_event(self._released[i])
             self._released[i] = None
         on_device = any(isinstance(t, torch.Tensor) and t.is_cuda for t in (matrices, scales)) or \
-            any(c.world_view_transform.is_cuda for c in (cameras or {}).values())
+            any(c.world_view_transform.is_cuda for v in (cameras or {}).values()
+                for c in (v if isinstance(v, (list, tuple)) else [v])) or \
+            any(isinstance(t, torch.Tensor) and t.is_cuda for t in (extrinsics or {}).values())
         if on_device:
             st.wait_stream(cur)  # the poses were produced by what the current stream holds
         with torch.cuda.stream(st):
-            frames = loop.step(matrices, scales, cameras, ensure=ensure)
+            frames = loop.step(matrices, scales, cameras, ensure=ensure, extrinsics=extrinsics)
             ev = torch.cuda.Event()
             ev.record(st)
         self._events[i] = ev

@@ -444,6 +444,27 @@ __device__ __forceinline__ bool quadrant_may_hit(float cx, float cy, const float
 
 // sigmoid of the raw-parameter path (forward and backward use the same value)
 __device__ __forceinline__ float sigmoid_canonical(float x) { return 1.0f / (1.0f + exp_canonical(-x)); }
+
+// Inverse of a 3 x 3 matrix in binary64 as adjugate / det, in the order the point cloud's C2W (pointcloud.hip) and the
+// sensor cameras (camera.hip) both state in their header comments:
+//   c00 = a11 a22 - a12 a21,  c01 = a12 a20 - a10 a22,  c02 = a10 a21 - a11 a20,  det = (a00 c00 + a01 c01) + a02 c02
+//   r0 = (c00, a02 a21 - a01 a22, a01 a12 - a02 a11) / det
+//   r1 = (c01, a00 a22 - a02 a20, a02 a10 - a00 a12) / det
+//   r2 = (c02, a01 a20 - a00 a21, a00 a11 - a01 a10) / det
+__device__ __forceinline__ void gsr_inverse3_f64(const double (&a)[3][3], double (&r)[3][3]) {
+    const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1], c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2],
+                 c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+    const double det = (a[0][0] * c00 + a[0][1] * c01) + a[0][2] * c02;
+    r[0][0] = c00 / det;
+    r[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det;
+    r[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det;
+    r[1][0] = c01 / det;
+    r[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det;
+    r[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det;
+    r[2][0] = c02 / det;
+    r[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det;
+    r[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det;
+}
 #endif
 
 // ---- frames per launch (gsr_forward_batch) ------------------------------------------------------------------

@@ -79,15 +79,10 @@ struct PcArgs {
 static_assert(sizeof(PcArgs) <= 4096 - 128, "the point-cloud arguments must fit the 4 KiB kernarg segment");
 
 __device__ __forceinline__ void pc_c2w(const float *m, float *out) {
-    const double a00 = m[0], a01 = m[4], a02 = m[8];
-    const double a10 = m[1], a11 = m[5], a12 = m[9];
-    const double a20 = m[2], a21 = m[6], a22 = m[10];
+    const double a[3][3] = {{m[0], m[4], m[8]}, {m[1], m[5], m[9]}, {m[2], m[6], m[10]}};
     const double t0 = m[12], t1 = m[13], t2 = m[14];
-    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-    const double det = (a00 * c00 + a01 * c01) + a02 * c02;
-    const double r[3][3] = {{c00 / det, (a02 * a21 - a01 * a22) / det, (a01 * a12 - a02 * a11) / det},
-                            {c01 / det, (a00 * a22 - a02 * a20) / det, (a02 * a10 - a00 * a12) / det},
-                            {c02 / det, (a01 * a20 - a00 * a21) / det, (a00 * a11 - a01 * a10) / det}};
+    double r[3][3];
+    gsr_inverse3_f64(a, r);  // (gsr_internal.h: the cofactor formula below)
     for (int i = 0; i < 3; i++) {
         out[4 * i + 0] = (float)r[i][0];
         out[4 * i + 1] = (float)r[i][1];

@@ -226,6 +226,39 @@ void forward_batch(const py::list &frames) {
     TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
 }
 
+// ---- camera records from simulator extrinsics (gsworld_amd._C.pack_cameras / run_cameras) -----------------------------
+// Built once from (n, extrinsic, projection, out, offsets, rigid_sim2real (16 floats), scale_sim2real) -- buffers as device
+// addresses (0 = NULL) -- and run step after step while no buffer moves; a step pack runs it between its staging kernel and
+// its frames (StepPack.run_staged_cams).
+struct CamPack {
+    GsrSensorCameras spec;
+
+    explicit CamPack(const py::tuple &t) {
+        TORCH_CHECK(t.size() == 7, "CamPack: 7 values expected, got ", t.size());
+        auto P = [](const py::handle &h) { return reinterpret_cast<void *>((uintptr_t)h.cast<int64_t>()); };
+        std::memset(&spec, 0, sizeof(spec));
+        spec.struct_size = (int32_t)sizeof(GsrSensorCameras);
+        spec.n = t[0].cast<int32_t>();
+        spec.extrinsic = static_cast<const float *>(P(t[1]));
+        spec.projection = static_cast<const float *>(P(t[2]));
+        spec.out = static_cast<float *>(P(t[3]));
+        spec.offsets = static_cast<const int32_t *>(P(t[4]));
+        const py::list G = t[5].cast<py::list>();
+        TORCH_CHECK(G.size() == 16, "CamPack: rigid_sim2real is 16 values");
+        for (int i = 0; i < 16; i++) spec.rigid_sim2real[i] = G[i].cast<double>();
+        spec.scale_sim2real = t[6].cast<double>();
+    }
+    void launch(void *stream) {
+        const int rc = gsr_cameras_from_extrinsics(&spec, stream);
+        TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+    }
+    void run(int64_t device_index) {
+        const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+        c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+        launch(current_stream(dev));
+    }
+};
+
 // ---- the argument pack of a step, kept on this side (gsworld_amd._C.pack_batch) ---------------------------------------
 // A loop that renders the SAME frames step after step (same tensors, settings and state; the per-step values live in device
 // buffers the kernels read) parsed its 39-value tuples again on every call of forward_batch: ~10 us of host per step, and in
@@ -283,6 +316,18 @@ struct StepPack {
                                       reinterpret_cast<float *>((uintptr_t)dst), (int32_t)K, (int32_t)mat_off,
                                       (int32_t)scale_off, reinterpret_cast<float *>((uintptr_t)table), stream);
         TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+        launch(stream);
+    }
+    // ... with the camera records of the staged extrinsics written in between (the frames read them)
+    void run_staged_cams(int64_t n, int64_t src, int64_t dst, int64_t K, int64_t mat_off, int64_t scale_off, int64_t table,
+                         CamPack &cams) {
+        c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+        void *stream = current_stream(dev);
+        const int rc = gsr_stage_step((int32_t)n, reinterpret_cast<const float *>((uintptr_t)src),
+                                      reinterpret_cast<float *>((uintptr_t)dst), (int32_t)K, (int32_t)mat_off,
+                                      (int32_t)scale_off, reinterpret_cast<float *>((uintptr_t)table), stream);
+        TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+        cams.launch(stream);
         launch(stream);
     }
 };
@@ -634,7 +679,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<StepPack>(m, "StepPack")
         .def(py::init<const py::list &>())
         .def("run", &StepPack::run)
-        .def("run_staged", &StepPack::run_staged);
+        .def("run_staged", &StepPack::run_staged)
+        .def("run_staged_cams", &StepPack::run_staged_cams);
+    py::class_<CamPack>(m, "CamPack").def(py::init<const py::tuple &>()).def("run", &CamPack::run);
     m.def("frame_stats", &frame_stats);
     m.def("render_maps", &render_maps);
     py::class_<CloudPack>(m, "CloudPack").def(py::init<const py::tuple &>()).def("run", &CloudPack::run);

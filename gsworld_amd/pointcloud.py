@@ -142,6 +142,9 @@ def prepare(depth, labels, frames, cameras, spec: PointCloudSpec, depth_scale: f
         names = list(range(len(cams)))
     if not cams:
         raise ValueError("at least one camera")
+    # (a camera may be a list: environment e's own camera at [e], one image size -- ClosedLoopRenderer(per_env_cameras=True))
+    env_cams = [list(c) if isinstance(c, (list, tuple)) else None for c in cams]
+    cams = [ec[0] if ec else c for c, ec in zip(cams, env_cams)]
     deps = _per_camera(depth, names, "depth")
     labs = _per_camera(labels, names, "labels")
     rgbs = _per_camera(frames, names, "frames")
@@ -155,18 +158,23 @@ def prepare(depth, labels, frames, cameras, spec: PointCloudSpec, depth_scale: f
     if spec.exclude_labels and any(l is None for l in labs):
         raise ValueError("exclude_labels needs every camera's label map")
     keep, vms = [], []
-    for cam, d, l, r in zip(cams, deps, labs, rgbs):
+    for cam, ec, d, l, r in zip(cams, env_cams, deps, labs, rgbs):
         H, W = int(cam.image_height), int(cam.image_width)
         _check(d, torch.float32, (E, H, W), dev, "depth")
         if l is not None:
             _check(l, torch.int16, (E, H, W), dev, "labels")
         if r is not None:
             _check(r, torch.uint8, (E, H, W, 3), dev, "frames")
-        vm = cam.world_view_transform
-        if vm.device != dev or vm.dtype != torch.float32 or not vm.is_contiguous():
-            vm = vm.detach().to(dev, torch.float32).contiguous()
-            keep.append(vm)
-        vms.append(vm)
+        if ec is not None and (len(ec) != E or any((int(c.image_width), int(c.image_height)) != (W, H) for c in ec)):
+            raise ValueError(f"a per-environment camera list needs {E} cameras of one image size")
+        per = []
+        for c in (ec if ec is not None else [cam] * E):
+            vm = c.world_view_transform
+            if vm.device != dev or vm.dtype != torch.float32 or not vm.is_contiguous():
+                vm = vm.detach().to(dev, torch.float32).contiguous()
+                keep.append(vm)
+            per.append((vm, c.tanfovx, c.tanfovy))
+        vms.append(per)
     N = sum(int(c.image_width) * int(c.image_height) for c in cams)
     S = N if spec.mode == _lib.PC_DENSE else int(spec.num_points)
     if out is None:
@@ -180,8 +188,9 @@ def prepare(depth, labels, frames, cameras, spec: PointCloudSpec, depth_scale: f
     views = []
     for e in range(E):
         for c, cam in enumerate(cams):
-            views.append(dict(width=cam.image_width, height=cam.image_height, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy,
-                              viewmatrix=vms[c], depth=deps[c][e], depth_scale=float(depth_scale),
+            vm, tx, ty = vms[c][e]
+            views.append(dict(width=cam.image_width, height=cam.image_height, tanfovx=tx, tanfovy=ty,
+                              viewmatrix=vm, depth=deps[c][e], depth_scale=float(depth_scale),
                               label=labs[c][e] if labs[c] is not None else None,
                               rgb8=rgbs[c][e] if rgbs[c] is not None else None))
     bits = spec.exclusion_bitmap()
@@ -215,7 +224,8 @@ def render_pointcloud(depth, labels, frames, cameras, spec: PointCloudSpec, dept
     """The point cloud of E environments seen by C cameras, on the current stream (no synchronisation).
 
     ``cameras``: ``{name: ViewParams}`` (or a list) -- size, field of view and ``world_view_transform`` (read on the
-    device when it lives there; copied up otherwise).  ``depth``: per camera (E, H, W[, 1]) float32 depth maps as
+    device when it lives there; copied up otherwise); a camera may also be a list of E ViewParams of one image size,
+    environment e's own camera at [e].  ``depth``: per camera (E, H, W[, 1]) float32 depth maps as
     ``gsr_render_maps`` writes them (0.0 = no point), written with ``depth_scale``; ``labels``: per camera (E, H, W[, 1])
     int16 label maps, or None (segmentation -1); ``frames``: per camera (E, H, W, 3) uint8 frames, or None (rgb 0).  Per-
     camera arguments are dicts keyed like ``cameras`` or lists in its order.

@@ -20,6 +20,8 @@
  *   gsr_render_pointcloud  <->  the point-cloud observation (obs_mode pointcloud) the wrapper also leaves to SAPIEN's
  *                               meshes, plus the crop / FPS step point-cloud policies run after it: world-frame points
  *                               from the maps, the frame and the camera, sampled to a fixed size on the device
+ *   gsr_cameras_from_extrinsics <->  cam_maniskill2gs (gs_world_wrapper.py:277-325), per environment and camera, on the
+ *                               device from the simulator's extrinsic_cv
  *
  * Conventions: plain pointers and sizes only (no torch types); every data pointer is DEVICE memory on the
  * current HIP device unless marked [host]; all inputs are borrowed, contiguous, float32; `stream` is a
@@ -534,6 +536,34 @@ typedef struct GsrCloudSpec {
 } GsrCloudSpec;
 int gsr_pointcloud_workspace(const GsrCloudSpec *spec, int64_t *bytes);
 int gsr_render_pointcloud(const GsrCloudSpec *spec, void *stream);
+
+/*
+ * Cameras from simulator sensor poses (camera.hip: the full definition, evaluation order included, is its header comment).
+ * Per view k < n: the OpenCV world->camera extrinsic E = [A | t] of the simulator (ManiSkill get_sensor_params()
+ * extrinsic_cv) becomes the 36-float camera record the frames read -- world_view (16, = W2C^T) | full_proj (16) |
+ * centre (3) | pad (1, written 0) -- of the 3DGS camera GSWorld builds from it (gs_world_wrapper.py cam_maniskill2gs): the
+ * simulator camera placed at scale_sim2real x its position, left-multiplied by rigid_sim2real.  Binary64 throughout,
+ * rounded to binary32 once per output.  `projection` holds each view's getProjectionMatrix(0.01, 100, FoVx, FoVy)^T as
+ * float32 (fixed for a camera's lifetime).  View k reads extrinsic + offsets[3k] (12 floats, row-major 3 x 4),
+ * projection + offsets[3k + 1] (16 floats) and writes out + offsets[3k + 2] (36 floats); offsets NULL: 12 k, 16 k, 36 k.
+ * Offsets are not checked against any buffer (device memory): the caller owns them.  Extrinsics are read when the kernel
+ * runs.  One launch on `stream`, no allocation, no synchronisation: the call can be captured into a hipGraph.  Limits
+ * (else GSR_E_INVALID): struct_size, 1 <= n <= GSR_CAM_MAX_VIEWS, non-null extrinsic / projection / out, a finite
+ * non-zero scale_sim2real.
+ */
+#define GSR_CAM_MAX_VIEWS 4096
+#define GSR_CAM_RECORD_FLOATS 36
+typedef struct GsrSensorCameras {
+    int32_t struct_size;            /* sizeof(GsrSensorCameras): the library rejects a mismatch (GSR_E_INVALID) */
+    int32_t n;                      /* views */
+    const float *extrinsic;         /* (3,4) row-major world->camera matrices, float32 */
+    const float *projection;        /* 16 floats per view: the projection matrix transposed, row-major */
+    float *out;                     /* 36-float records */
+    const int32_t *offsets;         /* 3 n float offsets (extrinsic, projection, record) per view, or NULL (packed) */
+    double rigid_sim2real[16];      /* [host] row-major 4 x 4 */
+    double scale_sim2real;          /* [host] */
+} GsrSensorCameras;
+int gsr_cameras_from_extrinsics(const GsrSensorCameras *spec, void *stream);
 
 #ifdef __cplusplus
 }
