@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -88,10 +89,49 @@ def _require_gpu(t: torch.Tensor, what: str):
             f"{what} is on {t.device}: the MI355X rasterizer has no CPU path (tensors must live on a HIP device)")
 
 
+def appearance_args(appearance, P: int, device):
+    """An ``appearance`` argument -- ``(table (G,3,4) | (G,12), lut (L,) int, labels (P,) | None[, versions (G+1,) | None])`` --
+    as the tensors the library reads (GsrInputs.appearance*): float32 / int32, dense, on ``device``; labels None = the part
+    labels.  ``ValueError`` for anything else (checked before any device work)."""
+    if not isinstance(appearance, (tuple, list)) or len(appearance) not in (3, 4):
+        raise ValueError("appearance must be (table (G,3,4), lut (L,) int32, labels (P,) | None[, versions (G+1,) | None])")
+    table, lut, labels = appearance[:3]
+    versions = appearance[3] if len(appearance) == 4 else None
+    as_t = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(device, dt)  # noqa: E731
+    table = as_t(table, torch.float32)
+    if table.dim() not in (2, 3) or table.shape[-1] != (4 if table.dim() == 3 else 12) or \
+            (table.dim() == 3 and table.shape[1] != 3):
+        raise ValueError(f"appearance table must be (G,3,4) or (G,12), got {tuple(table.shape)}")
+    G = int(table.shape[0])
+    if not 1 <= G <= _lib.APPEARANCE_MAX_GROUPS:
+        raise ValueError(f"appearance: 1 <= G <= {_lib.APPEARANCE_MAX_GROUPS} groups, got {G}")
+    lut = as_t(lut, torch.int32).reshape(-1).contiguous()
+    if lut.numel() < 1:
+        raise ValueError("appearance LUT must have at least one entry")
+    if labels is not None:
+        labels = as_t(labels, torch.float32).reshape(-1).contiguous()
+        if labels.numel() != P:
+            raise ValueError(f"appearance labels must be ({P},), got {labels.numel()} values")
+    if versions is not None:
+        versions = as_t(versions, torch.int32).reshape(-1).contiguous()
+        if versions.numel() != G + 1:
+            raise ValueError(f"appearance versions must be (G + 1,) = ({G + 1},), got {versions.numel()} values")
+    return table.reshape(G, 12).contiguous(), lut, labels, versions
+
+
+def _app_tensors(appearance, e, ei):
+    """(table, lut, labels, versions) for the compiled binding: the empty tensors e (float32) / ei (int32) stand for NULL."""
+    if appearance is None:
+        return e, ei, e, ei
+    t, lut, lab, ver = appearance
+    return t, lut, lab if lab is not None else e, ver if ver is not None else ei
+
+
 def forward_raw(settings: GsrSettings, background, means3D, colors, opacity, scales, rotations, cov3D_precomp,
                 viewmatrix, projmatrix, sh, campos, out_color, out_invdepth, radii, geomBuffer, binningBuffer,
                 imgBuffer, r_capacity: int = 0, want_stats: bool = True, sh_rest=None, param_space: int = 0,
-                rgb8_out=None, parts=None, forward_only: bool | None = False, layout=None, overflow_mirror: int = 0):
+                rgb8_out=None, parts=None, forward_only: bool | None = False, layout=None, overflow_mirror: int = 0,
+                appearance=None):
     """Thin call into gsr_forward with caller-owned output and state tensors (no allocation here).
     ``overflow_mirror``: GsrOutputs.overflow_mirror as an address (0 = not wanted).
     ``sh_rest``: optional features_rest (P,M-1,3); ``sh`` is then features_dc (P,1,3) -- no per-frame concatenation.
@@ -103,11 +143,14 @@ def forward_raw(settings: GsrSettings, background, means3D, colors, opacity, sca
     (never an inference frame, whatever ``TUNING["forward_only"]`` forces for A/B runs).
     ``layout``: optional ``(cull_blocks (ceil(P/256),8) float32, orig_index (P,) int32 | None)`` -- block bounds for
     view-frustum culling and the original numbering of a permuted model (GsrInputs.cull_blocks / orig_index;
-    :mod:`gsworld_amd.layout` builds them)."""
+    :mod:`gsworld_amd.layout` builds them).
+    ``appearance``: optional ``(table (G,12) float32, lut (L,) int32, labels (P,) float32 | None, versions (G+1,) int32 |
+    None)`` as :func:`appearance_args` returns it -- per-group colour affines inside preprocess (GsrInputs.appearance*)."""
     dev = means3D.device
     if _ext is not None:
         st = settings
         e = torch.empty(0, device=dev)
+        ei = torch.empty(0, dtype=torch.int32, device=dev)
         nv, nr, ov = _ext.forward_frame(
             st.image_height, st.image_width, st.tanfovx, st.tanfovy, st.scale_modifier, st.sh_degree, st.sh_coeffs,
             bool(st.antialiasing), bool(st.debug), st.near_plane, background, means3D,
@@ -118,12 +161,12 @@ def forward_raw(settings: GsrSettings, background, means3D, colors, opacity, sca
             binningBuffer, imgBuffer,
             rgb8_out if rgb8_out is not None else torch.empty(0, dtype=torch.uint8, device=dev), int(r_capacity),
             bool(want_stats), int(param_space), _tuning_list(forward_only),
-            parts[0] if parts is not None else e, parts[1] if parts is not None else torch.empty(0, dtype=torch.int32, device=dev),
+            parts[0] if parts is not None else e, parts[1] if parts is not None else ei,
             parts[2] if parts is not None else e,
             parts[3] if (parts is not None and parts[3] is not None) else torch.empty(0, dtype=torch.uint8, device=dev),
             layout[0] if layout is not None else e,
-            layout[1] if (layout is not None and layout[1] is not None) else torch.empty(0, dtype=torch.int32, device=dev),
-            int(overflow_mirror or 0))
+            layout[1] if (layout is not None and layout[1] is not None) else ei,
+            int(overflow_mirror or 0), *_app_tensors(appearance, e, ei))
         stats = GsrFrameStats()
         stats.num_visible, stats.num_rendered, stats.overflow = nv, nr, ov
         return stats
@@ -131,7 +174,7 @@ def forward_raw(settings: GsrSettings, background, means3D, colors, opacity, sca
         settings, background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
         campos, out_color, out_invdepth, radii, geomBuffer, binningBuffer, imgBuffer, sh_rest=sh_rest,
         param_space=param_space, rgb8_out=rgb8_out, parts=parts, forward_only=forward_only, layout=layout,
-        overflow_mirror=overflow_mirror)
+        overflow_mirror=overflow_mirror, appearance=appearance)
     stats = GsrFrameStats()
     with torch.cuda.device(dev):
         check(lib().gsr_forward(C.byref(settings), C.byref(inp), C.byref(out), C.byref(buf), C.c_int64(r_capacity),
@@ -142,7 +185,7 @@ def forward_raw(settings: GsrSettings, background, means3D, colors, opacity, sca
 def _frame_structs(settings: GsrSettings, background, means3D, colors, opacity, scales, rotations, cov3D_precomp,
                    viewmatrix, projmatrix, sh, campos, out_color, out_invdepth, radii, geomBuffer, binningBuffer,
                    imgBuffer, sh_rest=None, param_space: int = 0, rgb8_out=None, parts=None,
-                   forward_only: bool | None = False, layout=None, overflow_mirror: int = 0):
+                   forward_only: bool | None = False, layout=None, overflow_mirror: int = 0, appearance=None):
     """The four argument structs of one frame (include/gsr.h) from tensors; the fifth value keeps the resize callbacks
     alive while the structs are in use."""
     settings.forward_only = int(bool(forward_only))
@@ -165,6 +208,12 @@ def _frame_structs(settings: GsrSettings, background, means3D, colors, opacity, 
             raise ValueError("layout: orig_index must be an int32 tensor of shape (P,)")
         inp.cull_blocks = _ptr(blocks)
         inp.orig_index = _ptr(orig) if orig is not None else None
+    if appearance is not None:
+        table, lut, labels, versions = appearance
+        inp.appearance, inp.appearance_lut, inp.appearance_lut_size = _ptr(table), _ptr(lut), int(lut.numel())
+        inp.appearance_groups = int(table.shape[0])
+        inp.appearance_versions = _ptr(versions) if versions is not None else None
+        inp.appearance_labels = _ptr(labels) if labels is not None else None
     out = GsrOutputs(_ptr(out_color), _ptr(out_invdepth), _ptr(radii),
                      _ptr(rgb8_out) if rgb8_out is not None else None, int(overflow_mirror) if overflow_mirror else None)
     cbs = (_resizer(geomBuffer, header=True), _resizer(binningBuffer), _resizer(imgBuffer))
@@ -216,7 +265,7 @@ def pack_batch(frames):
                 parts[3] if (parts is not None and parts[3] is not None) else eb,
                 layout[0] if layout is not None else e,
                 layout[1] if (layout is not None and layout[1] is not None) else ei,
-                int(f.get("overflow_mirror") or 0)))
+                int(f.get("overflow_mirror") or 0), *_app_tensors(f.get("appearance"), e, ei)))
         if hasattr(_ext, "StepPack"):
             return ("pack", _ext.StepPack(packed))  # (the argument structs filled once, kept on the C++ side)
         return ("ext", packed)

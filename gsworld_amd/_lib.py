@@ -77,7 +77,13 @@ class GsrInputs(C.Structure):
         ("part_transforms", C.c_void_p), ("part_count", C.c_int32), ("part_rescale", C.c_void_p),
         # optional block bounds for view-frustum culling + original numbering of a permuted model (gsworld_amd/layout.py)
         ("cull_blocks", C.c_void_p), ("orig_index", C.c_void_p),
+        # optional per-group colour affines inside preprocess (forward only; gsworld_amd/appearance.py)
+        ("appearance", C.c_void_p), ("appearance_lut", C.c_void_p), ("appearance_lut_size", C.c_int32),
+        ("appearance_groups", C.c_int32), ("appearance_versions", C.c_void_p), ("appearance_labels", C.c_void_p),
     ]
+
+
+APPEARANCE_MAX_GROUPS = 64  # include/gsr.h GSR_APPEARANCE_MAX_GROUPS
 
 
 RAW_OPACITY, RAW_SCALES, RAW_ROTATIONS = 1, 2, 4  # include/gsr.h GSR_RAW_*

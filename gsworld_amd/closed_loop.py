@@ -103,7 +103,7 @@ class ClosedLoopRenderer:
                  background=None, fuse_transform: bool = True, growth: float = 2.0, bound_capacity="auto",
                  layout: bool = True, min_capacity: int | None = None, share_model_of=None, batched: bool = True,
                  keep_float: bool = False, block_cache: bool = True, tile_reuse: bool = True, maps=(),
-                 depth_scale: float = 1.0, pointcloud=None, per_env_cameras: bool = False, sim2real=None):
+                 depth_scale: float = 1.0, pointcloud=None, per_env_cameras: bool = False, sim2real=None, appearance=None):
         """``raw``: :class:`gsworld_amd.scenes.RawGaussians` (or any object with the same raw parameter tensors, e.g. a
         merged semantic model's ``_xyz`` ... under those names); ``part_labels``: part name -> semantic label(s), in
         the order the pose matrices will arrive; ``cameras``: name -> :class:`gsworld_amd.camera.ViewParams`;
@@ -164,8 +164,25 @@ class ClosedLoopRenderer:
         one camera per name for every environment, as the reference's wrapper does (environment 0's sensor pose).
         ``sim2real``: ``(rigid_sim2real (4,4), scale_sim2real)`` of the wrapper -- needed to hand over the simulator's
         ``extrinsic_cv`` directly (:meth:`set_extrinsics`): the camera records are then computed on the device in the
-        step itself (include/gsr.h ``gsr_cameras_from_extrinsics``)."""
+        step itself (include/gsr.h ``gsr_cameras_from_extrinsics``).
+        ``appearance``: ``{group name: label or labels}`` -- per-environment appearance randomization (include/gsr.h
+        ``GsrInputs.appearance``; :mod:`gsworld_amd.appearance`): the Gaussians of each named group (and group 0, everything
+        else) take their environment's colour affine, and every environment has its own background colour.  Tables and
+        backgrounds start at the identity and ``background``, and are set with :meth:`set_appearance` or ``step(appearance=)``
+        -- they travel in the step's staging vector, so every step mode reads them.  ``background`` may then also be
+        ``(E, 3)``.  With the default None nothing changes."""
         maps = tuple(maps or ())
+        if appearance is not None:
+            from .appearance import check_groups
+
+            sem = getattr(raw, "semantics", None)
+            sem = getattr(raw, "_semantics", None) if sem is None else sem
+            self._app_names, app_lut, self._app_G = check_groups(
+                appearance, sem.detach().cpu().numpy() if isinstance(sem, torch.Tensor) else sem)
+            if background is not None and tuple(torch.as_tensor(background).shape) not in ((3,), (int(num_envs), 3)):
+                raise ValueError(f"background must be (3,) or ({int(num_envs)}, 3) with appearance")
+        else:
+            self._app_names, app_lut, self._app_G = None, None, 0
         self.per_env_cameras = bool(per_env_cameras)
         E0 = int(num_envs)
         cam_lists = {n: _camera_list(n, v, E0, self.per_env_cameras) for n, v in cameras.items()}
@@ -258,7 +275,8 @@ class ClosedLoopRenderer:
             if self._map_kinds_run else None
         self.maps = {n: {m: b[m] for m in self.map_kinds} for n, b in self._map_bufs.items()} if self.map_kinds else None
         self._maps_pack = None  # (the gsr_render_maps arguments of the lanes, and the state addresses they were built for)
-        self.bg = torch.zeros(3, device=dev) if background is None else background.to(dev, torch.float32)
+        if appearance is None:
+            self.bg = torch.zeros(3, device=dev) if background is None else background.to(dev, torch.float32)
         # the loop never differentiates a frame: inference frames (GsrSettings.forward_only), no radii array
         lanes = self.num_envs * len(self.cameras)
         if bound_capacity == "auto":
@@ -305,7 +323,18 @@ class ClosedLoopRenderer:
         for n in self._ext_segs:
             self._seg[n] = (off, off + 12 * self._ecam)
             off += 12 * self._ecam
-        self._seg_order = ["poses"] + self.names + self._ext_segs
+        # with appearance: per environment its G x 12 table and background (may come from device tensors) and, apart, the
+        # G + 1 version words of the block cache (always from the host: the loop draws them)
+        G = self._app_G
+        app_segs = []
+        if G:
+            self._app_stride, self._ver_stride = G * 12 + 4, (G + 1 + 3) // 4 * 4
+            self._seg["app"] = (off, off + self.num_envs * self._app_stride)
+            off = self._seg["app"][1]
+            self._seg["appver"] = (off, off + self.num_envs * self._ver_stride)
+            off = self._seg["appver"][1]
+            app_segs = ["app", "appver"]
+        self._seg_order = ["poses"] + self.names + self._ext_segs + app_segs
         self._stage = torch.zeros(off, device=dev)
         self._host = torch.zeros(off)
         pin = dev.type == "cuda" and torch.cuda.is_available()
@@ -323,6 +352,12 @@ class ClosedLoopRenderer:
             for n in self._ext_segs:
                 o = self._seg[n][0]
                 v[n] = buf[o:o + 12 * self._ecam].view(self._ecam, 3, 4)
+            if G:
+                lo, hi = self._seg["app"]
+                rows = buf[lo:hi].view(self.num_envs, self._app_stride)
+                v["app_tables"], v["app_bg"] = rows[:, :G * 12].view(self.num_envs, G, 3, 4), rows[:, G * 12:G * 12 + 3]
+                lo, hi = self._seg["appver"]
+                v["appver"] = buf[lo:hi].view(self.num_envs, self._ver_stride)
             return v
 
         self._hv, dv = views(self._host), views(self._stage)
@@ -335,6 +370,14 @@ class ClosedLoopRenderer:
         self._ring_np = [r.numpy() for r in self._ring]
         self._hv["matrices"].copy_(torch.eye(4).expand(*lead, 4, 4))
         self._hv["scales"].fill_(1.0)
+        if G:
+            import random
+
+            self._ver_next = random.getrandbits(23)
+            self._hv["app_tables"].copy_(torch.eye(3, 4).expand(self.num_envs, G, 3, 4))
+            if background is not None:
+                self._hv["app_bg"].copy_(torch.as_tensor(background).detach().to("cpu", torch.float32).expand(self.num_envs, 3))
+            self._new_versions(range(self.num_envs))
         from .camera import ViewParams
 
         self.env_cameras = {}
@@ -370,6 +413,13 @@ class ClosedLoopRenderer:
             self.pointcloud = self._cloud_pack[1]
         # device-resident pose buffers: what a GPU simulator hands over (ManiSkill link poses are device tensors)
         self.matrices, self.scales = dv["matrices"], dv["scales"]
+        if G:
+            # (environment e's frames read row block e, background e and version words e of the staging vector)
+            self._app_lut = torch.as_tensor(app_lut).to(dev)
+            self._app_labels = None if self.fuse_transform else \
+                semantics.detach().reshape(-1).to(dev, torch.float32).contiguous()  # (fused: the part labels)
+            self.bg = dv["app_bg"]
+            self.appearance_tables, self.appearance_backgrounds = dv["app_tables"], dv["app_bg"]
         # The 17-float pose table(s) the frames read (fuse_transform) live in one persistent buffer and are packed WHERE THE
         # POSES ARRIVE, not inside the step: host poses by the kernel that brings the step's host values to the device
         # (gsr_stage_step reads the pinned slot directly: one launch instead of an H2D copy + the pack kernel), device
@@ -443,7 +493,7 @@ class ClosedLoopRenderer:
                 for c in range(C):
                     views.append(self.env_cameras[self.names[c]][e])
                     outs.append(self.frames[self.names[c]][e])
-                    per_lane.append(dict(parts=parts if E == 1 else parts[e]))
+                    per_lane.append(dict(parts=parts if E == 1 else parts[e], **self._app_lane(e)))
             self.multi.render(views, self.xyz, self.opacity, rgb8_out=outs, shs=self.features_dc,
                               shs_rest=self.features_rest, scales=self.scaling, rotations=self.rotation,
                               param_space=RAW_SCALES | RAW_ROTATIONS | self._model_version, bg=self.bg, per_lane=per_lane,
@@ -465,14 +515,70 @@ class ClosedLoopRenderer:
         if E == 1:
             self.multi.render(views, xyz, self.opacity, rgb8_out=outs, shs=self.features_dc,
                               shs_rest=self.features_rest, scales=scaling, rotations=rot,
-                              param_space=RAW_SCALES | RAW_ROTATIONS, bg=self.bg)
+                              param_space=RAW_SCALES | RAW_ROTATIONS, bg=self.bg,
+                              per_lane=[self._app_lane(0) for _ in range(C)] if self._app_G else None)
         else:
-            per_lane = [dict(means3D=xyz[e], scales=(scaling[e] if scaling.dim() == 3 else scaling), rotations=rot[e])
-                        for e in range(E) for _ in range(C)]
+            per_lane = [dict(means3D=xyz[e], scales=(scaling[e] if scaling.dim() == 3 else scaling), rotations=rot[e],
+                             **self._app_lane(e)) for e in range(E) for _ in range(C)]
             self.multi.render(views, None, self.opacity, rgb8_out=outs, shs=self.features_dc,
                               shs_rest=self.features_rest, param_space=RAW_SCALES | RAW_ROTATIONS, bg=self.bg,
                               per_lane=per_lane)
         self._run_maps()
+
+    def _app_lane(self, e: int) -> dict:
+        """The per-lane render arguments of environment e's appearance (device views of the staging vector), or {}."""
+        if not self._app_G:
+            return {}
+        return dict(appearance=(self._dv["app_tables"][e], self._app_lut, self._app_labels,
+                                self._dv["appver"][e, :self._app_G + 1].view(torch.int32)),
+                    bg=self._dv["app_bg"][e])
+
+    def _new_versions(self, env_ids):
+        """Fresh block-cache version words for these environments (every group and the whole table): what a table handed
+        over promises to the frames (include/gsr.h GsrInputs.appearance_versions) -- bit patterns of floats in [1, 2), so that
+        the staging copy moves them as they are."""
+        words = self._hv_np["appver"].view(np.uint32)
+        G = self._app_G
+        for e in env_ids:
+            for k in range(G + 1):
+                self._ver_next = (self._ver_next + 1) & 0x7FFFFF
+                words[e, k] = 0x3F800000 | self._ver_next
+        self._dirty.add("appver")
+
+    def set_appearance(self, tables, backgrounds=None, env_ids=None):
+        """Appearance of the next steps: ``tables`` ``(n, G, 3, 4)`` float32 colour affines (group 0 first, then the named
+        groups in the order given at construction; :class:`gsworld_amd.appearance.AppearanceRandomizer` draws them) and
+        optional ``backgrounds`` ``(n, 3)``, for all environments (n = E) or the ``env_ids`` given (a partial reset), on the
+        host or the device.  Host values travel with the step's other host values (no synchronisation, no re-capture);
+        device values are copied device to device -- the first of them on a loop with staged graphs makes the next step
+        capture once more, as device poses do, and host values after device ones read the segment back once (a blocking
+        copy).  Every table handed over counts as changed: the frames of those environments recompute their blocks once
+        (block cache, tile reuse), then keep them while the table rests."""
+        if not self._app_G:
+            raise ValueError("set_appearance needs a loop built with appearance={group name: labels}")
+        from .appearance import check_tables
+
+        t, b, ids = check_tables(tables, backgrounds, env_ids, self.num_envs, self._app_G)
+        for name, val, seg in (("app_tables", t, "app"), ("app_bg", b, "app")):
+            if val is None:
+                continue
+            if val.is_cuda:
+                self._flush()
+                for j, e in enumerate(ids):
+                    self._dv[name][e].copy_(val[j], non_blocking=True)
+                self._stale.add(seg)
+            else:
+                if seg in self._stale and seg not in self._dirty:
+                    # (the segment was last written from device tensors: its other rows are read back once -- a host
+                    #  synchronisation on the change from device to host tables only)
+                    lo, hi = self._seg[seg]
+                    self._host[lo:hi].copy_(self._stage[lo:hi].to("cpu"))
+                hv = self._hv_np[name]
+                src = val.detach().cpu().numpy()
+                for j, e in enumerate(ids):
+                    hv[e] = src[j]
+                self._dirty.add(seg)
+        self._new_versions(ids)
 
     def _run_cameras(self):
         """The records of the extrinsic-fed cameras from their staged extrinsics (``gsr_cameras_from_extrinsics``, one
@@ -716,10 +822,11 @@ class ClosedLoopRenderer:
         self._ext_set(self._ext_names + list(checked))
 
     def step(self, matrices: torch.Tensor | None = None, scales: torch.Tensor | None = None,
-             cameras: dict | None = None, ensure: bool = False, extrinsics: dict | None = None) -> dict:
+             cameras: dict | None = None, ensure: bool = False, extrinsics: dict | None = None, appearance=None) -> dict:
         """-> {camera name: uint8 (num_envs, H, W, 3)} -- renderer-owned tensors, overwritten by the next step.
 
-        ``cameras``: as :meth:`set_cameras`; ``extrinsics``: as :meth:`set_extrinsics` (this step's simulator sensor poses).
+        ``cameras``: as :meth:`set_cameras`; ``extrinsics``: as :meth:`set_extrinsics` (this step's simulator sensor poses);
+        ``appearance``: as :meth:`set_appearance` -- the ``(E, G, 3, 4)`` tables, or a dict of its keyword arguments.
 
         A lane whose instance list is sized from earlier frames (no ``bound_capacity``) can be outgrown by a later frame
         -- an arm swinging past a wrist camera triples the count -- and such a frame shows the background only.  That is
@@ -734,6 +841,11 @@ class ClosedLoopRenderer:
           mirror copy has landed (normally within a step or two); the loop then recovers as above -- the current step
           is rendered correctly -- and :attr:`late_overflow_frames` counts the frames that had already been handed out
           invalid."""
+        if appearance is not None:
+            if isinstance(appearance, dict):
+                self.set_appearance(**appearance)
+            else:
+                self.set_appearance(appearance)
         pre_k = None
         if self._graphs is not None and not self._stale and self._stage_fn is not None:
             # (None: not plain host tensors -- the general path)
@@ -997,6 +1109,8 @@ class PipelinedClosedLoop:
             raise ValueError("PipelinedClosedLoop does not render segmentation / depth maps: use ClosedLoopRenderer(maps=...)")
         if kw.get("pointcloud") is not None:
             raise ValueError("PipelinedClosedLoop does not make point clouds: use ClosedLoopRenderer(pointcloud=...)")
+        if kw.get("appearance") is not None:
+            raise ValueError("PipelinedClosedLoop does not randomize appearance: use ClosedLoopRenderer(appearance=...)")
         first = ClosedLoopRenderer(raw, part_labels, cameras, **kw)
         self.loops = [first] + [ClosedLoopRenderer(raw, part_labels, cameras, share_model_of=first, **kw)
                                 for _ in range(depth - 1)]

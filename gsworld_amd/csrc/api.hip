@@ -148,6 +148,19 @@ static int validate(const GsrSettings *st, const GsrInputs *in, const GsrOutputs
             return GSR_E_INVALID;
         }
     }
+    if (in->appearance || in->appearance_groups != 0) {
+        if (!st->forward_only) {
+            gsr_set_error("gsr_forward: the appearance transform (GsrInputs.appearance) is forward-only: set "
+                          "GsrSettings.forward_only");
+            return GSR_E_INVALID;
+        }
+        if (in->appearance_groups < 1 || in->appearance_groups > GSR_APPEARANCE_MAX_GROUPS || !in->appearance ||
+            !in->appearance_lut || in->appearance_lut_size < 1 || (!in->appearance_labels && !in->part_labels)) {
+            gsr_set_error("gsr_forward: appearance needs 1 <= appearance_groups <= 64, a table, a LUT of at least one entry "
+                          "and per-Gaussian labels (appearance_labels or part_labels)");
+            return GSR_E_INVALID;
+        }
+    }
     if (!buf->geom_resize || !buf->binning_resize || !buf->image_resize) {
         gsr_set_error("gsr_forward: resize callbacks are required");
         return GSR_E_INVALID;
@@ -259,7 +272,8 @@ int run_frames(int B, const GsrSettings *st, const GsrInputs *in, const GsrOutpu
         // block cache (preprocess.hip prep_block_cached): inference frames of the default path whose caller vouches for the model
         f.pc = GSR_PREP_BLOCK_CACHE && infer && band && mode == 1 && !p.radix_depth && ((uint32_t)in[k].param_space >> 8) != 0u &&
                in[k].part_labels != nullptr && in[k].cull_blocks != nullptr && out[k].radii == nullptr &&
-               in[k].part_count <= GSR_PC_MAX_PARTS;
+               in[k].part_count <= GSR_PC_MAX_PARTS &&
+               (in[k].appearance == nullptr || in[k].appearance_versions != nullptr);  // (colours: versions or no cache)
         // tile reuse (render.hip): ... whose only output is the uint8 frame, in a buffer the caller says nobody else writes
         f.td = GSR_TILE_REUSE && f.pc && super && (in[k].param_space & GSR_FRAME_KEPT) != 0 && out[k].out_rgb8 != nullptr &&
                out[k].out_color == nullptr && out[k].out_invdepth == nullptr;

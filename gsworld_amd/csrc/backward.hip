@@ -762,6 +762,10 @@ extern "C" int gsr_backward(const GsrSettings *st, const GsrInputs *in, const Gs
         gsr_set_error("gsr_backward: the in-preprocess part transform (GsrInputs.part_labels) is forward-only");
         return GSR_E_INVALID;
     }
+    if (in->appearance || in->appearance_groups != 0) {
+        gsr_set_error("gsr_backward: the appearance transform (GsrInputs.appearance) is forward-only");
+        return GSR_E_INVALID;
+    }
     if ((in->param_space & (GSR_RAW_SCALES | GSR_RAW_ROTATIONS)) && in->cov3D_precomp) {
         gsr_set_error("gsr_backward: raw scales / rotations cannot be combined with cov3D_precomp");
         return GSR_E_INVALID;

@@ -105,7 +105,9 @@ struct GsrHeader {
 #endif
 #define GSR_PC_MAGIC 0x50434348u  // 'PCCH'
 #define GSR_PC_MAX_PARTS 64
-#define GSR_PC_SLOT (40 + 17 * GSR_PC_MAX_PARTS)  // floats of one slot: view 16 | proj 16 | campos 3 | pad 5 | pose table
+// floats of one slot: view 16 | proj 16 | campos 3 | bg 3 | td_sig | pad | pose table | appearance versions (G + 1 words)
+#define GSR_PC_APP (40 + 17 * GSR_PC_MAX_PARTS)
+#define GSR_PC_SLOT (GSR_PC_APP + 68)
 // The one thread that compared R with the capacity.  Every frame clears hdr->overflow before its first such check, and a
 // path with two checks per frame (bin-then-sort) must count the frame once: only the 0 -> 1 edge counts.
 // `mirror` (GsrOutputs.overflow_mirror: two words the HOST can read, or nullptr) receives (of_magic, overflow_frames) as

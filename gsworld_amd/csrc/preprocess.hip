@@ -61,6 +61,12 @@ struct PreprocessArgs {
     uint32_t *tile_dirty;
     const float *bg;
     uint32_t td_sig;
+    // optional appearance transform (GsrInputs.appearance*; app == nullptr: off): per-group colour affines, label -> group by
+    // app_lut, the group's version word (app_ver[k], app_ver[app_groups] for the whole table) for the block cache
+    const float *app, *app_labels;
+    const int32_t *app_lut;
+    const uint32_t *app_ver;
+    int app_lut_size, app_groups;
 };
 
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -389,14 +395,33 @@ __device__ __forceinline__ GeomOut prep_geometry(const PreprocessArgs &a, int i,
     return o;
 }
 
+// The appearance group of a label (include/gsr.h GsrInputs.appearance): outside the LUT, or a LUT entry outside [0, G): 0.
+__device__ __forceinline__ int prep_app_group(const PreprocessArgs &a, const int label) {
+    const int k = (label >= 0 && label < a.app_lut_size) ? a.app_lut[label] : 0;
+    return (k >= 0 && k < a.app_groups) ? k : 0;
+}
+
+// c'_j = max(((M[j][0] r + M[j][1] g) + M[j][2] b) + t[j], 0): round-to-nearest multiplies and adds in this order, never an
+// FMA (a NumPy float32 restatement matches bit for bit; the identity row returns c >= 0 unchanged).  __fmul_rn / __fadd_rn are
+// plain * / + in this compiler, so the function forbids contraction itself instead of relying on the build's -ffp-contract=off.
+__device__ __forceinline__ void prep_appearance(const PreprocessArgs &a, const int g, float &cr, float &cg, float &cb) {
+#pragma clang fp contract(off)
+    const float *T = a.app + 12 * prep_app_group(a, (int)a.app_labels[g]);
+    const float r = cr, gg = cg, b = cb;
+    cr = fmaxf(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], r), __fmul_rn(T[1], gg)), __fmul_rn(T[2], b)), T[3]), 0.f);
+    cg = fmaxf(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], r), __fmul_rn(T[5], gg)), __fmul_rn(T[6], b)), T[7]), 0.f);
+    cb = fmaxf(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], r), __fmul_rn(T[9], gg)), __fmul_rn(T[10], b)), T[11]), 0.f);
+}
+
 // SH -> RGB (or the precomputed colour) of visible Gaussian g at position pp.xyz; writes rec2 and the clamp flags.
+// APP: launches in which some frame carries an appearance table (an instance of its own: the off path keeps its code)
 #ifndef GSR_PREP_GROUP_HALVES
 #define GSR_PREP_GROUP_HALVES 1  // (A/B: the multi-frame kernel's SH coefficients in two batches; see prep_colour)
 #endif
 // (HALVES: the coefficients are requested in two batches instead of one -- half the registers in flight, one more round
 //  trip.  The multi-frame kernel takes it: its loop over the frames costs the compiler registers, and the second and
 //  later frames of a group find the coefficients in this CU's cache.  Same products, same order: same colours.)
-template <bool FAST_SH16, bool HALVES = false>
+template <bool FAST_SH16, bool HALVES = false, bool APP = false>
 __device__ __forceinline__ void prep_colour(const PreprocessArgs &a, const int g, const float4 pp) {
     float cr, cg, cb;
     uint32_t clamp_bits = 0;
@@ -505,6 +530,7 @@ __device__ __forceinline__ void prep_colour(const PreprocessArgs &a, const int g
         clamp_bits = (cr < 0.f ? 1u : 0u) | (cg < 0.f ? 0x100u : 0u) | (cb < 0.f ? 0x10000u : 0u);
         cr = fmaxf(cr, 0.f); cg = fmaxf(cg, 0.f); cb = fmaxf(cb, 0.f);
     }
+    if (APP && a.app != nullptr) prep_appearance(a, g, cr, cg, cb);  // (wave-uniform: one frame per wave)
     a.splat[3 * (size_t)g + 2] = make_float4(cr, cg, cb, pp.w);
     if (!a.infer) a.clamped[g] = clamp_bits;
 }
@@ -653,7 +679,7 @@ typedef float PrepWorld[11][GSR_BLOCK];  // (multi-frame groups only: WorldGauss
 
 // One frame of the group on this workgroup's block.  have_world: an earlier frame of the group left the block's WorldGauss
 // in LDS (computed under pose table w_table and scale modifier w_mod); more: a later frame will want it.
-template <bool FAST_SH16, bool COUNT_TILES, bool MULTI, bool MARK = false>
+template <bool FAST_SH16, bool COUNT_TILES, bool MULTI, bool MARK = false, bool APP = false>
 __device__ __forceinline__ void prep_frame(const PreprocessArgs &a, const int i, const uint32_t blk, const bool have_world,
                                            const float *w_table, const float w_mod, const bool more, PrepShared &sh,
                                            PrepWorld *world, uint32_t *s_tcnt, const int mark = 0) {
@@ -735,7 +761,7 @@ __device__ __forceinline__ void prep_frame(const PreprocessArgs &a, const int i,
         }
     }
     if (threadIdx.x < cnt) {
-        prep_colour<FAST_SH16, MULTI && GSR_PREP_GROUP_HALVES>(a, sh.idx[threadIdx.x], sh.pos[threadIdx.x]);
+        prep_colour<FAST_SH16, MULTI && GSR_PREP_GROUP_HALVES, APP>(a, sh.idx[threadIdx.x], sh.pos[threadIdx.x]);
     }
 }
 
@@ -753,12 +779,27 @@ __device__ __forceinline__ void prep_frame(const PreprocessArgs &a, const int i,
 // of this launch reads is written during it.  Every other preprocess launch on the state (several frames per workgroup,
 // training frames, the A/B paths) clears the mark.  What it saves on the configs[2] surrogate: the static right_cam's share of
 // the two-frame launch, 39 -> 27 us per step.  Frames are bit-identical by construction (tests/test_closed_loop_gpu.py).
+// Appearance (GsrInputs.appearance, the APP instances): colours are part of the records, so (4) also asks for the version word
+// of the block's group (one label) -- a block of several labels is never kept and, when the table's word changed, marks every
+// member's tiles instead of the moved members' only.  Why tile reuse then stays exact: render.hip composites exactly the tiles
+// whose tile_dirty word carries this frame's token; a recomputed block under an unchanged camera marks the rects its members
+// had in the previous frame (before they are rewritten, prep_live_frames) and the rects they have now (prep_frame) -- so a
+// Gaussian whose colour changed has its old and new tiles composited.  A block that is kept has its group's word, hence
+// (caller's promise) its colours, unchanged; colour decides nothing of list membership or order.  Every tile left unmarked
+// therefore lists the records of the previous frame, colours included, in the same order.  A changed background clears
+// frame_same (lanes 35..37): every tile is composited.  (tests/test_appearance_gpu.py holds this against a loop without
+// block cache and tile reuse.)
 // ---------------------------------------------------------------------------------------------------------
 // (one WAVE asks, a lane per compared word -- 35 of the camera, 17 of the pose row: two loads per lane; the first version had
 //  every thread of every workgroup walk all 52 -- 39 -> 50 us instead of 39 -> 27)
 // -> bit 0: the block keeps its records; bit 1: camera, background and everything in the signature are the previous frame's
 // (what the tile reuse asks: a recomputed block then marks the tiles it touches instead of every tile being composited);
-// bit 2: the block's members carry different labels
+// bit 2: the block's members carry different labels (and, APP, the appearance table's word is unchanged: an unchanged pose row
+// then means unchanged records, prep_gaussian_moved)
+// APP (a frame with an appearance table and versions): lane 56 compares the version word of what the block's colours depend on
+// -- its group's word when its members carry one label (named by cull_blocks and read through the appearance LUT), the whole
+// table's word otherwise -- with the previous frame's (the caller's promise: a changed row comes with changed words)
+template <bool APP = false>
 __device__ __forceinline__ uint32_t prep_block_cached(const PreprocessArgs &a, const uint32_t blk) {
     const GsrHeader *h = a.hdr;
     const int lane = gsr_lane();
@@ -789,14 +830,22 @@ __device__ __forceinline__ uint32_t prep_block_cached(const PreprocessArgs &a, c
     } else if (lane < 56 && moving) {
         cur = __float_as_uint(a.part_transforms[(size_t)part * 17 + (lane - 39)]);
         was = prev[40 + 17 * part + (lane - 39)];
+    } else if (APP && lane == 56 && a.app != nullptr) {
+        // (labels of their own: cull_blocks names the part label of the block, not theirs -- the table's word)
+        const int w = (one_label && a.app_labels == a.part_labels) ? prep_app_group(a, (int)lf) : a.app_groups;
+        cur = a.app_ver[w];
+        was = prev[GSR_PC_APP + w];
     }
     const uint64_t differ = __builtin_amdgcn_ballot_w64(cur != was);
     // (the records know nothing of background and output buffer -- lanes 35..38; the pixels nothing of the pose rows)
     const bool kept = valid && one_label && (differ & ~(0xFull << 35)) == 0ull;
     const bool frame_same = valid && (differ & ((1ull << 39) - 1ull)) == 0ull;
-    return (kept ? 1u : 0u) | (frame_same ? 2u : 0u) | (one_label ? 0u : 4u);
+    // (a block of several labels whose colours may have changed marks every member's tiles, not only the moved ones')
+    const bool recolour = APP && (differ & (1ull << 56)) != 0ull;
+    return (kept ? 1u : 0u) | (frame_same ? 2u : 0u) | ((one_label || recolour) ? 0u : 4u);
 }
-// workgroup 0: this frame's camera and pose table into the slot that is NOT current
+// workgroup 0: this frame's camera and pose table (APP: and appearance versions) into the slot that is NOT current
+template <bool APP = false>
 __device__ __forceinline__ void prep_cache_publish(const PreprocessArgs &a) {
     GsrHeader *h = a.hdr;
     // (a state without a valid mark: which slot is "current" does not matter, nobody reads either)
@@ -813,6 +862,7 @@ __device__ __forceinline__ void prep_cache_publish(const PreprocessArgs &a) {
     }
     if (tid == 3) reinterpret_cast<uint32_t *>(cur)[38] = a.td_sig;
     for (int k = tid; k < 17 * a.part_count; k += GSR_BLOCK) cur[40 + k] = a.part_transforms[k];
+    if (APP && a.app != nullptr && tid <= a.app_groups) reinterpret_cast<uint32_t *>(cur)[GSR_PC_APP + tid] = a.app_ver[tid];
     if (tid == 0) {
         h->pc_sig_next = a.pc_sig;
         h->pc_pending = GSR_PC_MAGIC;
@@ -822,7 +872,7 @@ __device__ __forceinline__ void prep_cache_publish(const PreprocessArgs &a) {
 
 // the block's view-frustum test for every frame of the group -> the frames that have to look at it; the others get their
 // zero count (and, where a caller reads them, zero radii) on the spot
-template <bool CACHE = true, bool TD = CACHE>
+template <bool CACHE = true, bool TD = CACHE, bool APP = false>
 __device__ __forceinline__ uint32_t prep_live_frames(const PrepLaunch &L, const int f0, const int nf, const uint32_t blk,
                                                      const int i, PrepShared &sh) {
     uint32_t live = (1u << nf) - 1u;
@@ -830,14 +880,14 @@ __device__ __forceinline__ uint32_t prep_live_frames(const PrepLaunch &L, const 
     // workgroup 0 leaves the camera and poses of the frames that take the block cache for their next frames
     if (CACHE && blk == 0u)
         for (int k = 0; k < nf; k++)
-            if (L.bt.f[f0 + k].pc_slots != nullptr) prep_cache_publish(L.bt.f[f0 + k]);
+            if (L.bt.f[f0 + k].pc_slots != nullptr) prep_cache_publish<APP>(L.bt.f[f0 + k]);
     // (a wave evaluates the block's test for its frames, ~100 instructions each; the verdicts meet at a barrier.  A lone
     //  frame's cache question is asked by the last wave meanwhile, a group's frames ask theirs behind their frustum test.)
     constexpr int NW = GSR_BLOCK / GSR_WAVE;
     for (int k = gsr_wave(); k < nf; k += NW) {
         const PreprocessArgs a = L.bt.f[f0 + k];
         const bool c = prep_block_culled(a, (int)blk);
-        const uint32_t h = (CACHE && nf > 1 && a.pc_slots != nullptr) ? prep_block_cached(a, blk) : 0u;
+        const uint32_t h = (CACHE && nf > 1 && a.pc_slots != nullptr) ? prep_block_cached<APP>(a, blk) : 0u;
         if (gsr_lane() == 0) {
             sh.culled[k] = c ? 1 : 0;
             if (nf > 1) {
@@ -849,7 +899,7 @@ __device__ __forceinline__ uint32_t prep_live_frames(const PrepLaunch &L, const 
     }
     if (CACHE && nf == 1 && gsr_wave() == NW - 1) {
         const PreprocessArgs &a = L.bt.f[f0];
-        const uint32_t h = a.pc_slots != nullptr ? prep_block_cached(a, blk) : 0u;
+        const uint32_t h = a.pc_slots != nullptr ? prep_block_cached<APP>(a, blk) : 0u;
         if (gsr_lane() == 0) {
             sh.cached[0] = (int)h;
             if (TD && blk == 0u && a.tile_dirty != nullptr)
@@ -900,7 +950,7 @@ __device__ __forceinline__ uint32_t prep_live_frames(const PrepLaunch &L, const 
 #endif
 // (TD: some frame of the launch marks tiles for the compositor's tile reuse -- an instance of its own: the marking costs the
 //  single-frame kernel its 72nd register, i.e. a wave per SIMD, which frames without it must not pay)
-template <bool FAST_SH16, bool COUNT_TILES, bool TD = false>
+template <bool FAST_SH16, bool COUNT_TILES, bool TD = false, bool APP = false>
 __global__ __launch_bounds__(GSR_BLOCK)
 #if GSR_PREP_MAX_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(1, GSR_PREP_MAX_WAVES)))
@@ -917,8 +967,8 @@ void preprocess_kernel(const PrepLaunch L) {
     }
     if (a.pc_slots == nullptr && blk == 0u && threadIdx.x == 0)
         a.hdr->pc_magic = 0u;  // (this launch rewrites the records without leaving its camera: nothing to compare with next)
-    if (prep_live_frames<true, TD>(L, f0, 1, blk, i, sh) == 0u) return;  // (+ the block cache: cull_blocks is there whenever pc_slots is)
-    prep_frame<FAST_SH16, COUNT_TILES, false, TD>(a, i, blk, false, nullptr, 0.f, false, sh, nullptr, s_tcnt,
+    if (prep_live_frames<true, TD, APP>(L, f0, 1, blk, i, sh) == 0u) return;  // (+ the block cache: cull_blocks is there whenever pc_slots is)
+    prep_frame<FAST_SH16, COUNT_TILES, false, TD, APP>(a, i, blk, false, nullptr, 0.f, false, sh, nullptr, s_tcnt,
                                                   (TD && a.tile_dirty != nullptr && (sh.cached[0] & 2) != 0)
                                                       ? ((sh.cached[0] & 4) != 0 ? 2 : 1) : 0);
 }
@@ -933,10 +983,16 @@ void preprocess_kernel(const PrepLaunch L) {
 #define GSR_PREP_GROUP_CACHE_WAVES 5  // waves per SIMD asked for the CACHE instance: 85 VGPRs, no scratch (0 = the same six as
                                       // the plain instance, with the scratch: four environments 13.12 against 13.23-13.33 k)
 #endif
-template <bool FAST_SH16, bool CACHE = false>
+// (CACHE with APP: the appearance words cost the frame loop more registers -- at five waves 96 VGPRs and 20 bytes of scratch;
+//  four waves, no scratch)
+#ifndef GSR_PREP_GROUP_APP_CACHE_WAVES
+#define GSR_PREP_GROUP_APP_CACHE_WAVES 4
+#endif
+template <bool FAST_SH16, bool CACHE = false, bool APP = false>
 __global__
 #if GSR_PREP_GROUP_WAVES > 0
-__launch_bounds__(GSR_BLOCK, (CACHE && GSR_PREP_GROUP_CACHE_WAVES > 0) ? GSR_PREP_GROUP_CACHE_WAVES : GSR_PREP_GROUP_WAVES)
+__launch_bounds__(GSR_BLOCK, (CACHE && APP) ? GSR_PREP_GROUP_APP_CACHE_WAVES
+                            : (CACHE && GSR_PREP_GROUP_CACHE_WAVES > 0) ? GSR_PREP_GROUP_CACHE_WAVES : GSR_PREP_GROUP_WAVES)
 #else
 __launch_bounds__(GSR_BLOCK)
 #endif
@@ -948,7 +1004,7 @@ void preprocess_group_kernel(const PrepLaunch L) {
     const int i0 = (int)blk * GSR_BLOCK + (int)threadIdx.x;
     if (blk == 0u && (int)threadIdx.x < nf && L.bt.f[f0 + (int)threadIdx.x].pc_slots == nullptr)
         L.bt.f[f0 + (int)threadIdx.x].hdr->pc_magic = 0u;  // (a frame that rewrites its records without leaving its camera)
-    const uint32_t live = prep_live_frames<CACHE>(L, f0, nf, blk, i0, sh);
+    const uint32_t live = prep_live_frames<CACHE, CACHE, APP>(L, f0, nf, blk, i0, sh);
     if (live == 0u) return;
     // ---- the frames that see the block, one after the other; what no camera enters is kept between them -- in LDS, each
     // thread its own slots (in registers the eleven words would stay live across the colour phase, whose 48 SH
@@ -963,7 +1019,7 @@ void preprocess_group_kernel(const PrepLaunch L) {
         // (the Gaussian's number is made opaque per frame: otherwise every address of the body is hoisted out of the loop)
         int i = i0;
         asm volatile("" : "+v"(i));
-        prep_frame<FAST_SH16, false, true, CACHE>(a, i, blk, have_world, w_table, w_mod, (live >> (k + 1)) != 0u, sh, &s_world,
+        prep_frame<FAST_SH16, false, true, CACHE, APP>(a, i, blk, have_world, w_table, w_mod, (live >> (k + 1)) != 0u, sh, &s_world,
                                                   nullptr, (CACHE && a.tile_dirty != nullptr && (sh.cached[k] & 2) != 0)
                                                                ? ((sh.cached[k] & 4) != 0 ? 2 : 1) : 0);
         have_world = true;
@@ -1007,7 +1063,7 @@ static bool prep_same_model(const PreprocessArgs &x, const PreprocessArgs &y) {
 
 int gsr_launch_preprocess(int B, GsrFrame *fr, bool count_tiles, bool infer, hipStream_t stream) {
     PreprocessArgs args[GSR_MAX_BATCH];
-    bool fast = true;
+    bool fast = true, app = false;
     for (int k = 0; k < B; k++) {
         const GsrSettings &st = *fr[k].st;
         const GsrInputs &in = *fr[k].in;
@@ -1065,6 +1121,13 @@ int gsr_launch_preprocess(int B, GsrFrame *fr, bool count_tiles, bool infer, hip
         a.td_sig = 0u;
         a.tile_dirty = (fr[k].pc && fr[k].td) ? fr[k].img.tile_dirty : (uint32_t *)nullptr;
         a.bg = in.background;
+        a.app = in.appearance;
+        a.app_labels = in.appearance_labels != nullptr ? in.appearance_labels : in.part_labels;
+        a.app_lut = in.appearance_lut;
+        a.app_ver = in.appearance_versions;
+        a.app_lut_size = in.appearance_lut_size;
+        a.app_groups = in.appearance_groups;
+        app = app || in.appearance != nullptr;
         if (fr[k].pc) {
             a.pc_slots = g.pc_slots;
             // everything but camera and poses that the records depend on (FNV-1a over the values)
@@ -1084,6 +1147,13 @@ int gsr_launch_preprocess(int B, GsrFrame *fr, bool count_tiles, bool infer, hip
             mix(ptrs, sizeof(ptrs));
             mix(ints, sizeof(ints));
             mix(flts, sizeof(flts));
+            if (in.appearance != nullptr) {  // (where the colour transform comes from; its values are the version words' matter)
+                const uintptr_t aptrs[] = {(uintptr_t)in.appearance, (uintptr_t)in.appearance_lut, (uintptr_t)a.app_labels,
+                                           (uintptr_t)in.appearance_versions};
+                const int32_t aints[] = {in.appearance_lut_size, in.appearance_groups};
+                mix(aptrs, sizeof(aptrs));
+                mix(aints, sizeof(aints));
+            }
             a.pc_sig = hsh;
             // ... and what the tile reuse depends on beyond camera and background: where the frame goes (a word of the slot
             // by itself: a caller that rotates its output buffers keeps its blocks, it just composites every tile)
@@ -1128,7 +1198,16 @@ int gsr_launch_preprocess(int B, GsrFrame *fr, bool count_tiles, bool infer, hip
     if (groups < B) {  // (some frames share a model; count_tiles frames never do)
         bool cache = false;
         for (int k = 0; k < B; k++) cache = cache || L.bt.f[k].pc_slots != nullptr;
-        if (fast && cache)
+        if (app) {
+            if (fast && cache)
+                hipLaunchKernelGGL((preprocess_group_kernel<true, true, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+            else if (fast)
+                hipLaunchKernelGGL((preprocess_group_kernel<true, false, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+            else if (cache)
+                hipLaunchKernelGGL((preprocess_group_kernel<false, true, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+            else
+                hipLaunchKernelGGL((preprocess_group_kernel<false, false, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+        } else if (fast && cache)
             hipLaunchKernelGGL((preprocess_group_kernel<true, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
         else if (fast)
             hipLaunchKernelGGL((preprocess_group_kernel<true, false>), grid, dim3(GSR_BLOCK), 0, stream, L);
@@ -1137,14 +1216,27 @@ int gsr_launch_preprocess(int B, GsrFrame *fr, bool count_tiles, bool infer, hip
         else
             hipLaunchKernelGGL((preprocess_group_kernel<false, false>), grid, dim3(GSR_BLOCK), 0, stream, L);
     } else if (count_tiles) {
-        if (fast)
+        if (app && fast)
+            hipLaunchKernelGGL((preprocess_kernel<true, true, false, true>), grid, dim3(GSR_BLOCK), lds, stream, L);
+        else if (app)
+            hipLaunchKernelGGL((preprocess_kernel<false, true, false, true>), grid, dim3(GSR_BLOCK), lds, stream, L);
+        else if (fast)
             hipLaunchKernelGGL((preprocess_kernel<true, true>), grid, dim3(GSR_BLOCK), lds, stream, L);
         else
             hipLaunchKernelGGL((preprocess_kernel<false, true>), grid, dim3(GSR_BLOCK), lds, stream, L);
     } else {
         bool td = false;
         for (int k = 0; k < B; k++) td = td || L.bt.f[k].tile_dirty != nullptr;
-        if (fast && td)
+        if (app) {
+            if (fast && td)
+                hipLaunchKernelGGL((preprocess_kernel<true, false, true, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+            else if (fast)
+                hipLaunchKernelGGL((preprocess_kernel<true, false, false, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+            else if (td)
+                hipLaunchKernelGGL((preprocess_kernel<false, false, true, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+            else
+                hipLaunchKernelGGL((preprocess_kernel<false, false, false, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
+        } else if (fast && td)
             hipLaunchKernelGGL((preprocess_kernel<true, false, true>), grid, dim3(GSR_BLOCK), 0, stream, L);
         else if (fast)
             hipLaunchKernelGGL((preprocess_kernel<true, false>), grid, dim3(GSR_BLOCK), 0, stream, L);

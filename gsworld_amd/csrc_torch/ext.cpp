@@ -120,7 +120,8 @@ void fill_frame(FrameCall &f, int H, int W, double tanfovx, double tanfovy, doub
                 const torch::Tensor &image, const torch::Tensor &rgb8_out, int param_space,
                 const std::vector<int> &tuning, const torch::Tensor &part_labels, const torch::Tensor &part_lut,
                 const torch::Tensor &part_table, const torch::Tensor &part_rescale, const torch::Tensor &cull_blocks,
-                const torch::Tensor &orig_index, int64_t overflow_mirror) {
+                const torch::Tensor &orig_index, int64_t overflow_mirror, const torch::Tensor &app_table,
+                const torch::Tensor &app_lut, const torch::Tensor &app_labels, const torch::Tensor &app_versions) {
     f.st = settings(H, W, (float)tanfovx, (float)tanfovy, (float)scale_modifier, degree, M, false, antialiasing, debug,
                     (float)near_plane, tuning_from(tuning));
     GsrInputs in{};
@@ -154,6 +155,15 @@ void fill_frame(FrameCall &f, int H, int W, double tanfovx, double tanfovy, doub
         TORCH_CHECK(orig_index.numel() == means3D.size(0), "orig_index must be (P,)");
         in.orig_index = orig_index.data_ptr<int32_t>();
     }
+    if (app_table.numel() != 0) {  // per-group colour affines inside preprocess (GsrInputs.appearance*; the library checks the rest)
+        TORCH_CHECK(app_table.numel() % 12 == 0, "appearance table must be (G, 12)");
+        in.appearance = fptr(app_table);
+        in.appearance_groups = (int32_t)(app_table.numel() / 12);
+        in.appearance_lut = app_lut.numel() ? app_lut.data_ptr<int32_t>() : nullptr;
+        in.appearance_lut_size = (int32_t)app_lut.numel();
+        in.appearance_labels = app_labels.numel() ? fptr(app_labels) : nullptr;
+        in.appearance_versions = app_versions.numel() ? reinterpret_cast<const uint32_t *>(app_versions.data_ptr<int32_t>()) : nullptr;
+    }
     f.in = in;
     f.out = GsrOutputs{out_color.numel() ? out_color.data_ptr<float>() : nullptr,
                        out_invdepth.numel() ? out_invdepth.data_ptr<float>() : nullptr,
@@ -176,14 +186,15 @@ std::tuple<int64_t, int64_t, int64_t> forward_frame(
     const torch::Tensor &rgb8_out, int64_t r_capacity, bool want_stats, int param_space, std::vector<int> tuning,
     const torch::Tensor &part_labels, const torch::Tensor &part_lut, const torch::Tensor &part_table,
     const torch::Tensor &part_rescale, const torch::Tensor &cull_blocks, const torch::Tensor &orig_index,
-    int64_t overflow_mirror) {
+    int64_t overflow_mirror, const torch::Tensor &app_table, const torch::Tensor &app_lut, const torch::Tensor &app_labels,
+    const torch::Tensor &app_versions) {
     const auto dev = means3D.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     FrameCall f;
     fill_frame(f, H, W, tanfovx, tanfovy, scale_modifier, degree, M, antialiasing, debug, near_plane, bg, means3D, colors,
                opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh, sh_rest, campos, out_color,
                out_invdepth, radii, geom, binning, image, rgb8_out, param_space, tuning, part_labels, part_lut, part_table,
-               part_rescale, cull_blocks, orig_index, overflow_mirror);
+               part_rescale, cull_blocks, orig_index, overflow_mirror, app_table, app_lut, app_labels, app_versions);
     GsrFrameStats stats{};
     const int rc = gsr_forward(&f.st, &f.in, &f.out, &f.buf, r_capacity, want_stats ? &stats : nullptr, current_stream(dev));
     TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
@@ -200,7 +211,7 @@ void forward_batch(const py::list &frames) {
     torch::Device dev(torch::kCPU);
     for (size_t k = 0; k < B; k++) {
         const py::tuple t = frames[k].cast<py::tuple>();
-        TORCH_CHECK(t.size() == 39, "forward_batch: a frame is a tuple of 39 values, got ", t.size());
+        TORCH_CHECK(t.size() == 43, "forward_batch: a frame is a tuple of 43 values, got ", t.size());
         auto T = [&](int i) { return t[i].cast<torch::Tensor>(); };
         if (k == 0) dev = T(11).device();
         caps[k] = t[29].cast<int64_t>();
@@ -208,7 +219,8 @@ void forward_batch(const py::list &frames) {
                    t[4].cast<double>(), t[5].cast<int>(), t[6].cast<int>(), t[7].cast<bool>(), t[8].cast<bool>(),
                    t[9].cast<double>(), T(10), T(11), T(12), T(13), T(14), T(15), T(16), T(17), T(18), T(19), T(20), T(21),
                    T(22), T(23), T(24), T(25), T(26), T(27), T(28), t[30].cast<int>(), t[31].cast<std::vector<int>>(),
-                   T(32), T(33), T(34), T(35), T(36), T(37), t[38].cast<int64_t>());
+                   T(32), T(33), T(34), T(35), T(36), T(37), t[38].cast<int64_t>(), T(39),
+                   T(40), T(41), T(42));
     }
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     std::vector<GsrSettings> st(B);
@@ -261,7 +273,7 @@ struct CamPack {
 
 // ---- the argument pack of a step, kept on this side (gsworld_amd._C.pack_batch) ---------------------------------------
 // A loop that renders the SAME frames step after step (same tensors, settings and state; the per-step values live in device
-// buffers the kernels read) parsed its 39-value tuples again on every call of forward_batch: ~10 us of host per step, and in
+// buffers the kernels read) parsed its 43-value tuples again on every call of forward_batch: ~10 us of host per step, and in
 // the closed loop's eager route 15 us of idle device between the staging kernel and preprocess (kernel trace, round 6).  The
 // pack keeps the filled argument structs; run() is gsr_forward_batch, run_staged() gsr_stage_step + gsr_forward_batch --
 // one call from Python for everything a step enqueues.
@@ -282,7 +294,7 @@ struct StepPack {
         caps.resize(B);
         for (size_t k = 0; k < B; k++) {
             const py::tuple t = frames[k].cast<py::tuple>();
-            TORCH_CHECK(t.size() == 39, "StepPack: a frame is a tuple of 39 values, got ", t.size());
+            TORCH_CHECK(t.size() == 43, "StepPack: a frame is a tuple of 43 values, got ", t.size());
             auto T = [&](int i) { return t[i].cast<torch::Tensor>(); };
             if (k == 0) dev = T(11).device();
             caps[k] = t[29].cast<int64_t>();
@@ -290,7 +302,8 @@ struct StepPack {
                        t[4].cast<double>(), t[5].cast<int>(), t[6].cast<int>(), t[7].cast<bool>(), t[8].cast<bool>(),
                        t[9].cast<double>(), T(10), T(11), T(12), T(13), T(14), T(15), T(16), T(17), T(18), T(19), T(20), T(21),
                        T(22), T(23), T(24), T(25), T(26), T(27), T(28), t[30].cast<int>(), t[31].cast<std::vector<int>>(),
-                       T(32), T(33), T(34), T(35), T(36), T(37), t[38].cast<int64_t>());
+                       T(32), T(33), T(34), T(35), T(36), T(37), t[38].cast<int64_t>(), T(39),
+                   T(40), T(41), T(42));
         }
         st.resize(B); in.resize(B); out.resize(B); buf.resize(B);
         for (size_t k = 0; k < B; k++) {
@@ -538,7 +551,9 @@ rasterize_gaussians(const torch::Tensor &background, const torch::Tensor &means3
                                    param_space, tuning, torch::empty({0}, fopt),
                                    torch::empty({0}, means3D.options().dtype(torch::kInt32)), torch::empty({0}, fopt),
                                    torch::empty({0}, bopt), torch::empty({0}, fopt),
-                                   torch::empty({0}, means3D.options().dtype(torch::kInt32)), 0);
+                                   torch::empty({0}, means3D.options().dtype(torch::kInt32)), 0, torch::empty({0}, fopt),
+                                   torch::empty({0}, means3D.options().dtype(torch::kInt32)), torch::empty({0}, fopt),
+                                   torch::empty({0}, means3D.options().dtype(torch::kInt32)));
         (void)prefiltered;
         rendered = (int)std::get<1>(stats);
     }

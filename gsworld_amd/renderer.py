@@ -105,7 +105,7 @@ class FrameRenderer:
     def render(self, view, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                cov3D_precomp=None, bg=None, sh_degree: int = 3, scale_modifier: float = 1.0,
                antialiasing: bool = False, debug: bool = False, exact: bool = False, shs_rest=None,
-               param_space: int = 0, rgb8_out=None, parts=None, outputs=None, layout=None):
+               param_space: int = 0, rgb8_out=None, parts=None, outputs=None, layout=None, appearance=None):
         """Enqueue one frame; returns (color (3,H,W), radii (P,), invdepth (1,H,W)) -- tensors owned by the
         renderer and overwritten by the next call.  ``view`` is a :class:`gsworld_amd.camera.ViewParams` on device.
         ``shs_rest``: pass the model's two SH parameters as they are stored, ``shs=features_dc`` (P,1,3) and
@@ -123,12 +123,16 @@ class FrameRenderer:
         which preprocess skips the blocks of the model no tile can see, and, for a model stored in the layout's Morton
         order, the original numbering (radii, lists and depth ties stay those of the original model; bit-identical frames).
         ``outputs``: optional caller-owned ``(color (3,H,W) f32, invdepth (1,H,W) f32, radii (P,) i32)`` on this device,
-        written instead of the renderer's own buffers (every element is written)."""
+        written instead of the renderer's own buffers (every element is written).
+        ``appearance``: ``(table (G,3,4), lut (L,) int, labels (P,) | None[, versions (G+1,) int32 | None])`` -- per-group colour
+        affines applied to every Gaussian's colour inside preprocess (include/gsr.h ``GsrInputs.appearance``; forward_only
+        renderers only): Gaussian i is in group ``lut[int(labels[i])]`` (0 outside the LUT; labels None = the part labels of
+        ``parts``).  ``versions`` drive the block cache of model-versioned frames (a changed row needs changed words)."""
         call, color, radii, invd = self._prepare(
             view, means3D, opacities, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
             cov3D_precomp=cov3D_precomp, bg=bg, sh_degree=sh_degree, scale_modifier=scale_modifier,
             antialiasing=antialiasing, debug=debug, exact=exact, shs_rest=shs_rest, param_space=param_space,
-            rgb8_out=rgb8_out, parts=parts, outputs=outputs, layout=layout)
+            rgb8_out=rgb8_out, parts=parts, outputs=outputs, layout=layout, appearance=appearance)
         cap = call["r_capacity"]
         stats = _C.forward_raw(want_stats=(cap == 0), **call)
         self._finish(cap, stats)
@@ -137,7 +141,7 @@ class FrameRenderer:
     def _prepare(self, view, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                  cov3D_precomp=None, bg=None, sh_degree: int = 3, scale_modifier: float = 1.0,
                  antialiasing: bool = False, debug: bool = False, exact: bool = False, shs_rest=None,
-                 param_space: int = 0, rgb8_out=None, parts=None, outputs=None, layout=None):
+                 param_space: int = 0, rgb8_out=None, parts=None, outputs=None, layout=None, appearance=None):
         """Everything of :meth:`render` before the call into the library (same arguments): tensors normalised, outputs
         and capacity chosen.  -> (keyword arguments of ``_C.forward_raw`` for this frame, color, radii, invdepth)."""
         dev = self.device
@@ -173,6 +177,10 @@ class FrameRenderer:
             raise ValueError("means3D must have dimensions (num_points, 3)")
         P = means3D.shape[0]
         H, W = view.image_height, view.image_width
+        if appearance is not None:
+            appearance = _C.appearance_args(appearance, P, dev)
+            if appearance[2] is None and parts is None:
+                raise ValueError("appearance: labels are required without parts (the part labels)")
         if outputs is not None:
             color, invd, radii = outputs
             rad = radii if radii is not None else torch.empty((P,), dtype=torch.int32, device=dev)
@@ -219,7 +227,7 @@ class FrameRenderer:
             sh=shs if shs is not None else empty, campos=campos, out_color=color, out_invdepth=invd, radii=radii,
             geomBuffer=self.geom, binningBuffer=self.binning, imgBuffer=self.image, r_capacity=cap, sh_rest=shs_rest,
             param_space=param_space, rgb8_out=rgb8_out, parts=parts, forward_only=self.forward_only, layout=layout,
-            overflow_mirror=(self._mirror_dev or 0) if not self.bounded else 0)
+            overflow_mirror=(self._mirror_dev or 0) if not self.bounded else 0, appearance=appearance)
         if not self.want_float and outputs is None:
             color = invd = None  # (what the caller gets back; the call holds the empty tensors = NULL images)
         # (what render_maps needs to find its way through the frame's state: the plan follows from these)

@@ -156,14 +156,43 @@ typedef struct GsrInputs {
      * default sort / placement path only. */
     const float *cull_blocks;      /* (ceil(P / 256), 8) or NULL */
     const int32_t *orig_index;     /* (P) or NULL */
+    /* Optional appearance transform (forward only: a frame without GsrSettings.forward_only that sets it is refused,
+     * GSR_E_INVALID): per-group colour affines applied inside preprocess, for visual domain randomization per environment
+     * and episode without a model copy.  Gaussian i belongs to group k = appearance_lut[label] with label =
+     * (int)appearance_labels[i] (or (int)part_labels[i] when appearance_labels is NULL); a label outside the LUT, or a LUT
+     * entry outside [0, G), is group 0 (the "rest").  Row k of `appearance` is the row-major 3 x 4 affine [M | t], and the
+     * colour preprocess computed (max(sh + 0.5, 0), or colors_precomp) becomes, per channel j = r, g, b,
+     *     c'_j = max(((M[j][0] r + M[j][1] g) + M[j][2] b) + t[j], 0)
+     * in round-to-nearest binary32 multiplies and adds in exactly this order, never contracted to an FMA (no upper clamp:
+     * out_rgb8 clamps at 255, out_color keeps the value).  The identity row gives the same colour bit for bit (c >= 0).
+     * appearance_versions (G + 1 words, or NULL) drives the block cache of GSR_MODEL_VERSION frames: word k < G describes
+     * row k, word G the whole table.  Nonzero G with versions is the caller's promise, in the style of GSR_MODEL_VERSION, that
+     * a row whose floats differ from the previous frame's on this state comes with a different word k AND a different word G;
+     * a block of one label then keeps its records while its group's word is unchanged, a block of several labels while the
+     * table's word is, and the tiles of every recomputed block are composited again (GSR_FRAME_KEPT).  NULL versions: every
+     * block is recomputed.  The LUT and the label array are not covered by the words: like part_lut and part_labels they fall
+     * under the GSR_MODEL_VERSION promise -- rewriting either in place under an unchanged model version gives stale blocks
+     * (pick a new model version, or new arrays, when they change).  The arrays (table, LUT, labels) are read when the frame
+     * runs.
+     * appearance == NULL and appearance_groups == 0: off (the frame is what it was without these fields).  Otherwise
+     * 1 <= appearance_groups <= GSR_APPEARANCE_MAX_GROUPS, a non-NULL LUT with appearance_lut_size >= 1 and a label array are
+     * required (else GSR_E_INVALID). */
+    const float *appearance;             /* (appearance_groups, 12) or NULL */
+    const int32_t *appearance_lut;       /* (appearance_lut_size) label -> group */
+    int32_t appearance_lut_size;
+    int32_t appearance_groups;           /* G */
+    const uint32_t *appearance_versions; /* (G + 1) or NULL */
+    const float *appearance_labels;      /* (P) or NULL: part_labels */
 } GsrInputs;
+#define GSR_APPEARANCE_MAX_GROUPS 64
 
 #define GSR_RAW_OPACITY 1   /* opacities are logits:        opacity  = 1 / (1 + exp(-x)) */
 #define GSR_RAW_SCALES 2    /* scales are log-scales:        scale    = exp(x) */
 #define GSR_RAW_ROTATIONS 4 /* rotations are un-normalised:  rotation = q / max(|q|, 1e-12) */
 /* Bits 8..31 of param_space: a MODEL VERSION, or 0.  Nonzero is the caller's promise that the model arrays (means3D, shs, shs_rest,
- * opacities, scales, rotations), part_labels, part_lut, part_rescale, cull_blocks and orig_index hold exactly what they held in the
- * previous frame on this state that carried the same version -- pick a fresh random value whenever any of them is written.
+ * opacities, scales, rotations), part_labels, part_lut, part_rescale, cull_blocks, orig_index, appearance_lut and appearance_labels
+ * hold exactly what they held in the previous frame on this state that carried the same version -- pick a fresh random value whenever
+ * any of them is written.
  * Inference frames (GsrSettings.forward_only, default path, radii == NULL) with part_labels and cull_blocks then leave a block of
  * 256 Gaussians as the previous frame on the state computed it when nothing the block's records depend on has changed: settings,
  * camera (view, projection, centre: bit for bit) and the pose row of the block's one part (csrc/preprocess.hip
