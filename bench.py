@@ -6,8 +6,12 @@ plus GSWorld's uint8 frame conversion, on a synthetic xarm6_align-like scene (1,
 sensor camera `right_cam`; BASELINE.json configs[1]).  Inputs are resident in HBM before the timed
 region.  N > 1: one independent scene per GPU (configs[3]); finished uint8 frames are gathered with RCCL.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs: set-up, W warm-up steps, K timed steps, the outputs of --dump-outputs and the
+line.  `--full` adds everything else the line has carried: the default frame every frame slot is checked against before
+and after the timed steps, per-stage and per-frame timings, the roofline, the secondary measurements and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -35,11 +39,16 @@ def parse():
     ap.add_argument("--gather-every", type=int, default=16, help="frames per RCCL gather batch (N > 1)")
     ap.add_argument("--collective", choices=["gather", "all_gather"], default="gather",
                     help="N > 1: gather-to-rank-0 (default, what north_star asks for) or all_gather of the uint8 frames")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the default frame every frame slot is checked against "
+                         "before and after the timed steps, per-stage and per-frame timings, the roofline, the secondary "
+                         "measurements and the CPU baselines.  Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements (dense view, upstream packing, closed loop, torch-CPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-frames", type=int, default=5)
-    ap.add_argument("--breakdown", action="store_true", help="print a per-stage event timing table to stderr")
+                    help="--full: skip the secondary measurements (dense view, upstream packing, closed loop, torch-CPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--cpu-frames", type=int, default=5, help="--full: frames of the CPU baseline")
+    ap.add_argument("--breakdown", action="store_true", help="--full: print a per-stage event timing table to stderr")
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step in a hipGraph")
     ap.add_argument("--render-bpc", type=int, default=0, help="persistent compositing workgroups per CU (0 = library default)")
     ap.add_argument("--no-layout", action="store_true",
@@ -56,9 +65,9 @@ def parse():
                     help="steps in flight: consecutive steps alternate over this many HIP streams, each with its own renderer "
                          "states (1 = every launch on one stream)")
     ap.add_argument("--only-steps", action="store_true",
-                    help="profiling aid: nothing but the step's own launches after the set-up (no one-frame-per-launch stage "
-                         "table, latency loop or one-frame figure), so that a rocprofv3 --stats average of this command is "
-                         "the average of the step's launches")
+                    help="--full, profiling aid: nothing but the step's own launches after the set-up (no one-frame-per-launch "
+                         "stage table, latency loop or one-frame figure), so that a rocprofv3 --stats average of this command "
+                         "is the average of the step's launches")
     ap.add_argument("--in-flight", type=int, default=0,
                     help="A/B of rounds 2-4: N frames in flight, ONE frame per step and stream (= --batch 1 --streams N)")
     a = ap.parse_args()
@@ -68,11 +77,14 @@ def parse():
         ap.error("--batch must be 1..8, --streams >= 1")
     if a.steps < 1 or a.blocks < 1:
         ap.error("--steps and --blocks must be >= 1")
+    if a.breakdown and not a.full:
+        ap.error("--breakdown needs --full (the stage table is a run of its own)")
     return a
 
 
 def main():
     args = parse()
+    full = args.full
     import torch
     import torch.distributed as dist
 
@@ -134,16 +146,17 @@ def main():
     n_groups = n_slots // B  # distinct steps (output slots) before the frame buffers are reused
     # inference frames (GsrSettings.forward_only): GSWorld's loop keeps ["render"] only (gs_world_wrapper.py:266-270) --
     # nothing a backward would read is written, instances are binned per 2 x 1 super-tile; the image is bit-identical
-    # (tests/test_renderer_gpu.py, and checked against a default frame right below)
+    # (tests/test_renderer_gpu.py, and in a --full run checked against a default frame right below)
     mcs = [MultiCameraRenderer(B, dev, batched=True, forward_only=True, want_radii=False) for _ in range(G)]
-    r1 = FrameRenderer(dev, forward_only=True, want_radii=False)   # one frame, one gsr_forward call (latency, stage table)
-    one_rgb8 = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
-    # N, V, R of SURVEY.md 8d's byte model are those of the reference's own per-tile pipeline: one default frame gives them
-    ref_r = FrameRenderer(dev)
-    ref_rgb8 = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
-    ref_r.render(cam, means, op, shs=shs, scales=sc, rotations=rot, bg=bg, rgb8_out=ref_rgb8, exact=True)
-    true_stats = ref_r.stats()
-    del ref_r
+    if full:
+        r1 = FrameRenderer(dev, forward_only=True, want_radii=False)   # one frame, one gsr_forward call (latency, stage table)
+        one_rgb8 = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
+        # N, V, R of SURVEY.md 8d's byte model are those of the reference's own per-tile pipeline: one default frame gives them
+        ref_r = FrameRenderer(dev)
+        ref_rgb8 = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
+        ref_r.render(cam, means, op, shs=shs, scales=sc, rotations=rot, bg=bg, rgb8_out=ref_rgb8, exact=True)
+        true_stats = ref_r.stats()
+        del ref_r
     kw = dict(shs=m_shs, scales=m_sc, rotations=m_rot, bg=bg, layout=lay)
     set_outs = [None] * G  # per renderer set: the (color, radii, invdepth) buffers its steps write (--dump-outputs)
 
@@ -161,15 +174,17 @@ def main():
         for _ in range(2):
             group(g)
             mcs[g].ensure_valid(lambda g=g: group(g))
-    for _ in range(2):
-        frame1()
-        r1.ensure_valid(frame1)
+    if full:
+        for _ in range(2):
+            frame1()
+            r1.ensure_valid(frame1)
     torch.cuda.synchronize()
-    for b in range(B):
-        if not torch.equal(fg.frames[b], ref_rgb8):
+    if full:
+        for b in range(B):
+            if not torch.equal(fg.frames[b], ref_rgb8):
+                raise SystemExit("forward_only frame differs from the default frame: result invalid")
+        if not torch.equal(one_rgb8, ref_rgb8):
             raise SystemExit("forward_only frame differs from the default frame: result invalid")
-    if not torch.equal(one_rgb8, ref_rgb8):
-        raise SystemExit("forward_only frame differs from the default frame: result invalid")
 
     # ---- hipGraph capture of every distinct step (launch-bound inner loop) ---------------------------------------
     graph = None
@@ -237,68 +252,71 @@ def main():
         done += n_k
     step_s = sorted(s / n for s, n in zip(block_s, block_n))
     elapsed = step_s[len(step_s) // 2] * args.steps  # (K steps at the median block's rate)
-    # Every frame slot is checked AGAIN behind the timed region, byte for byte against the default exact-mode frame: the
-    # routes a static camera earns only after several balanced frames (kept splitters taken blind, buckets of 1024 records,
-    # the previous frame's placement cuts, cooperative quadrants dealt by last frame's costs) are engaged in the timed
-    # steps, not in the frames checked before them (VERDICT round 5, weak #1d).  A mismatch fails the run.
-    verified_after = 0
-    for b in range(n_slots):
-        if not torch.equal(fg.frames[b], ref_rgb8):
-            raise SystemExit(f"frame slot {b} differs from the default frame AFTER the timed region: result invalid")
-        verified_after += 1
+    if full:
+        # Every frame slot is checked AGAIN behind the timed region, byte for byte against the default exact-mode frame: the
+        # routes a static camera earns only after several balanced frames (kept splitters taken blind, buckets of 1024
+        # records, the previous frame's placement cuts, cooperative quadrants dealt by last frame's costs) are engaged in
+        # the timed steps, not in the frames checked before them (VERDICT round 5, weak #1d).  A mismatch fails the run.
+        verified_after = 0
+        for b in range(n_slots):
+            if not torch.equal(fg.frames[b], ref_rgb8):
+                raise SystemExit(f"frame slot {b} differs from the default frame AFTER the timed region: result invalid")
+            verified_after += 1
     if args.dump_outputs and rank == 0:
         j = (done - 1) % n_groups  # the last timed step: its slots, and the buffers of its renderer set
         color, _, invd = zip(*set_outs[j % G])
         dump_outputs(args.dump_outputs, {"rgb8": fg.frames[j * B:(j + 1) * B], "color": torch.stack(color),
                                          "invdepth": torch.stack(invd)})
 
-    # ---- the dominant kernel's launch duration, HIP events on its launch stream: (a) the step's own launch (B frames
-    # per launch), eager on one stream; (b) one frame per launch.  Every stage of both (events cannot be recorded inside
-    # a replayed hipGraph)
-    def staged(fn, reps):
-        check(lib().gsr_profile_enable(2))
-        for _ in range(reps):
-            fn()
+    if full:
+        # ---- the dominant kernel's launch duration, HIP events on its launch stream: (a) the step's own launch (B frames
+        # per launch), eager on one stream; (b) one frame per launch.  Every stage of both (events cannot be recorded inside
+        # a replayed hipGraph)
+        def staged(fn, reps):
+            check(lib().gsr_profile_enable(2))
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+            pr = GsrProfile()
+            check(lib().gsr_profile_collect(pr))
+            check(lib().gsr_profile_enable(0))
+            return [pr.stage_ms[k] / max(pr.frames, 1) for k in range(len(PROFILE_STAGES))]
+
+        reps = min(args.steps, 200)
+        for _ in range(5):
+            group(0)
         torch.cuda.synchronize()
-        pr = GsrProfile()
-        check(lib().gsr_profile_collect(pr))
-        check(lib().gsr_profile_enable(0))
-        return [pr.stage_ms[k] / max(pr.frames, 1) for k in range(len(PROFILE_STAGES))]
+        stage_ms_step = staged(lambda: group(0), max(reps // B, 20))
+        stage_ms = staged(frame1, reps) if not args.only_steps else [0.0] * len(PROFILE_STAGES)
 
-    reps = min(args.steps, 200)
-    for _ in range(5):
-        group(0)
-    torch.cuda.synchronize()
-    stage_ms_step = staged(lambda: group(0), max(reps // B, 20))
-    stage_ms = staged(frame1, reps) if not args.only_steps else [0.0] * len(PROFILE_STAGES)
-
-    # per-frame latency distribution (hipEvent per frame, median and p95), strictly one frame at a time
-    g1 = None
-    if not args.no_graph and not args.only_steps:
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            frame1()
-        torch.cuda.current_stream().wait_stream(side)
-        g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1, stream=side):
-            frame1()
-    n_lat = min(max(args.steps, 100), 200) if not args.only_steps else 0
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_lat)]
-    for e0, e1 in ev:
-        e0.record()
-        g1.replay() if g1 is not None else frame1()
-        e1.record()
-    torch.cuda.synchronize()
-    lat = sorted(e0.elapsed_time(e1) for e0, e1 in ev) or [0.0]
-    frame_ms_p50, frame_ms_p95 = lat[len(lat) // 2], lat[min(len(lat) - 1, int(0.95 * len(lat)))]
+        # per-frame latency distribution (hipEvent per frame, median and p95), strictly one frame at a time
+        g1 = None
+        if not args.no_graph and not args.only_steps:
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                frame1()
+            torch.cuda.current_stream().wait_stream(side)
+            g1 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g1, stream=side):
+                frame1()
+        n_lat = min(max(args.steps, 100), 200) if not args.only_steps else 0
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_lat)]
+        for e0, e1 in ev:
+            e0.record()
+            g1.replay() if g1 is not None else frame1()
+            e1.record()
+        torch.cuda.synchronize()
+        lat = sorted(e0.elapsed_time(e1) for e0, e1 in ev) or [0.0]
+        frame_ms_p50, frame_ms_p95 = lat[len(lat) // 2], lat[min(len(lat) - 1, int(0.95 * len(lat)))]
 
     for g in range(G):
         if any(s_.overflow for s_ in mcs[g].ensure_valid(lambda: None)):
             raise SystemExit("binning capacity overflowed during the timed region: result invalid")
-    stats = r1.ensure_valid(frame1) if not args.only_steps else r1.stats()
-    if stats.overflow:
-        raise SystemExit("binning capacity overflowed during the timed region: result invalid")
+    if full:
+        stats = r1.ensure_valid(frame1) if not args.only_steps else r1.stats()
+        if stats.overflow:
+            raise SystemExit("binning capacity overflowed during the timed region: result invalid")
 
     own_elapsed = elapsed
     t_max = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -314,7 +332,7 @@ def main():
     # the same frame in other arrangements, for the line's config: strictly one frame at a time (the figure a caller
     # sees who needs frame k before it can ask for frame k + 1), and the step's B frames per launch on ONE stream
     one_fps = one_stream_fps = None
-    if rank == 0 and world == 1 and graph is not None:
+    if full and rank == 0 and world == 1 and graph is not None:
         one_fps = _time_frames(torch, g1.replay, min(max(args.steps, 100), 300))
         if G > 1:
             k_ = [0]
@@ -328,59 +346,11 @@ def main():
         else:
             one_stream_fps = fps
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if full and rank == 0 and world == 1 and not args.no_extras:
         extras = secondary_measurements(args, dev, raw, name, (means, shs, op, sc, rot),
                                         (m_means, m_shs, m_op, m_sc, m_rot, lay), bg, group_streams if G > 1 else None)
 
     if rank == 0:
-        binned = stats.num_rendered  # instances actually placed (super-tile lists)
-        stats = true_stats           # the byte model counts the reference's per-tile instances
-        b_alg = stats.algorithmic_bytes(W, H)
-        render_ms_step = stage_ms_step[-1]          # one launch of the step: B frames
-        render_ms = stage_ms[-1]                    # one launch of one frame
-        frame_render_bytes = 40 * stats.num_rendered + 16 * W * H  # 40 B per composited instance + outputs
-        render_bytes = B * frame_render_bytes
-        ach = render_bytes / (render_ms_step * 1e-3) / 1e9 if render_ms_step > 0 else 0.0
-        ach1 = frame_render_bytes / (render_ms * 1e-3) / 1e9 if render_ms > 0 else 0.0
-        traffic = valu_frac = None
-        traffic_source = "none"
-        pmc = os.path.join(ROOT, "profiles", "pmc_render.json")
-        if os.path.exists(pmc):
-            try:
-                rec = json.load(open(pmc))
-                traffic = rec.get("hbm_bytes_per_launch")
-                # NOT measured in this run (PMC counters need a rocprofv3 session): a committed counter run of the same
-                # launch.  The record carries the hash of render.hip it was taken with and the frames per launch; a
-                # kernel edited since then is flagged instead of silently quoted.
-                import hashlib
-                sha = hashlib.sha256(open(os.path.join(ROOT, "gsworld_amd", "csrc", "render.hip"), "rb").read()).hexdigest()[:16]
-                stale = rec.get("render_hip_sha16") != sha
-                per_launch = int(rec.get("frames_per_launch", 1))
-                if traffic is not None and per_launch != B:
-                    traffic = traffic * B / per_launch
-                traffic_source = (f"committed rocprofv3 --pmc run {os.path.relpath(pmc, ROOT)} "
-                                  f"({rec.get('collected', 'undated')}, {per_launch} frame(s) per launch"
-                                  f"{'' if per_launch == B else f', scaled to {B}'}; render.hip "
-                                  f"{'CHANGED since then: stale' if stale else 'unchanged since then'})")
-                # what actually bounds the compositor: VALU issue.  SQ_INSTS_VALU wave-instructions per frame (committed
-                # PMC run) x 4 cycles on 256 CUs x 4 SIMDs at the 2.13 GHz the stamps measured under this kernel
-                insts = rec.get("counters", {}).get("SQ_INSTS_VALU")
-                if insts and render_ms_step > 0:
-                    valu_frac = (insts / per_launch) * B * 4.0 / (256 * 4 * 2.13e9 * render_ms_step * 1e-3)
-            except Exception:  # noqa: BLE001
-                traffic = valu_frac = None
-        # the same kernel's average in the committed rocprofv3 --kernel-trace --stats run of this command (profiles/)
-        rocprof_ms = None
-        try:
-            import csv
-            import glob
-
-            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "round*", "kernel_stats_bench_step_launches.csv"))):
-                for row in csv.DictReader(open(path)):
-                    if "render_stream_kernel<true>" in row["Name"]:
-                        rocprof_ms = {"file": os.path.relpath(path, ROOT), "avg_ms": float(row["AverageNs"]) * 1e-6}
-        except Exception:  # noqa: BLE001
-            rocprof_ms = None
         total_fps = world * B * args.steps / sum(block_s)
         out = {
             "metric": "rendered frames/sec @640x480, 1.5M Gaussians",
@@ -390,25 +360,20 @@ def main():
             "config": {
                 "workload": f"{name}-like synthetic scene, {n} Gaussians, {W}x{H} right_cam, forward-only "
                             "(BASELINE.json configs[1]; one scene per GPU for N>1 = configs[3])",
-                "num_gaussians": n, "num_visible": stats.num_visible, "num_rendered": stats.num_rendered,
-                "binned_instances": binned,
+                "num_gaussians": n,
                 "step": f"one pass of the hot path over a batch of {B} frames: ONE gsr_forward_batch call = 10 kernel launches "
                         f"whose grids span the {B} frames (include/gsr.h); value = {B} x steps / time",
                 "frames_per_step": B, "steps_in_flight": G,
                 "frames_in_flight": B * G,
                 "frame_mode": "forward_only (inference: super-tile binning, no backward-only writes; image bit-identical "
-                              "to the default frame, checked in this run before AND after the timed region)",
-                "frame_slots_verified_after_timed_region": verified_after,
+                              "to the default frame, " + ("checked in this run before AND after the timed region)" if full else
+                                                          "checked by a --full run before and after the timed region)"),
                 "sh_degree": 3, "launch": "hipGraph replay" if graph is not None else "eager",
                 "comparability": "rounds 1-3: value = frames / total time, one frame per step, 1-3 frames in flight on "
                                  "streams; round 4: median of 5 blocks, 3 or 4 stream lanes picked by a trial in the run; "
                                  "round 5: fixed arrangement (flags --batch / --streams), median of >= 25 blocks, "
                                  "total-time figure beside it; since then: exactly --steps timed steps, one block "
                                  "unless --blocks splits them",
-                # the same frame: strictly one at a time / the step's launches on one stream / camera turned every frame
-                "one_frame_in_flight_frames_per_s": one_fps,
-                "one_stream_frames_per_s": one_stream_fps,
-                "moving_camera_frames_per_s": extras.get("moving_camera", {}).get("frames_per_s"),
                 "model_layout": ("Morton order per size class + block bounds built once per scene "
                                  f"(gsworld_amd/layout.py, {layout_s:.3f} s on this box, outside the timed region): "
                                  "preprocess skips the blocks of 256 Gaussians no tile can see; image, radii and tie "
@@ -428,7 +393,65 @@ def main():
                 # figure is directly comparable with the N = 1 run
                 "per_rank_frames_per_s": [B * args.steps / t for t in per_rank],
             },
-            "roofline": {
+        }
+        if full:
+            binned = stats.num_rendered  # instances actually placed (super-tile lists)
+            stats = true_stats           # the byte model counts the reference's per-tile instances
+            b_alg = stats.algorithmic_bytes(W, H)
+            render_ms_step = stage_ms_step[-1]          # one launch of the step: B frames
+            render_ms = stage_ms[-1]                    # one launch of one frame
+            frame_render_bytes = 40 * stats.num_rendered + 16 * W * H  # 40 B per composited instance + outputs
+            render_bytes = B * frame_render_bytes
+            ach = render_bytes / (render_ms_step * 1e-3) / 1e9 if render_ms_step > 0 else 0.0
+            ach1 = frame_render_bytes / (render_ms * 1e-3) / 1e9 if render_ms > 0 else 0.0
+            traffic = valu_frac = None
+            traffic_source = "none"
+            pmc = os.path.join(ROOT, "profiles", "pmc_render.json")
+            if os.path.exists(pmc):
+                try:
+                    rec = json.load(open(pmc))
+                    traffic = rec.get("hbm_bytes_per_launch")
+                    # NOT measured in this run (PMC counters need a rocprofv3 session): a committed counter run of the same
+                    # launch.  The record carries the hash of render.hip it was taken with and the frames per launch; a
+                    # kernel edited since then is flagged instead of silently quoted.
+                    import hashlib
+                    sha = hashlib.sha256(open(os.path.join(ROOT, "gsworld_amd", "csrc", "render.hip"), "rb").read()).hexdigest()[:16]
+                    stale = rec.get("render_hip_sha16") != sha
+                    per_launch = int(rec.get("frames_per_launch", 1))
+                    if traffic is not None and per_launch != B:
+                        traffic = traffic * B / per_launch
+                    traffic_source = (f"committed rocprofv3 --pmc run {os.path.relpath(pmc, ROOT)} "
+                                      f"({rec.get('collected', 'undated')}, {per_launch} frame(s) per launch"
+                                      f"{'' if per_launch == B else f', scaled to {B}'}; render.hip "
+                                      f"{'CHANGED since then: stale' if stale else 'unchanged since then'})")
+                    # what actually bounds the compositor: VALU issue.  SQ_INSTS_VALU wave-instructions per frame (committed
+                    # PMC run) x 4 cycles on 256 CUs x 4 SIMDs at the 2.13 GHz the stamps measured under this kernel
+                    insts = rec.get("counters", {}).get("SQ_INSTS_VALU")
+                    if insts and render_ms_step > 0:
+                        valu_frac = (insts / per_launch) * B * 4.0 / (256 * 4 * 2.13e9 * render_ms_step * 1e-3)
+                except Exception:  # noqa: BLE001
+                    traffic = valu_frac = None
+            # the same kernel's average in the committed rocprofv3 --kernel-trace --stats run of this command (profiles/)
+            rocprof_ms = None
+            try:
+                import csv
+                import glob
+
+                for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "round*", "kernel_stats_bench_step_launches.csv"))):
+                    for row in csv.DictReader(open(path)):
+                        if "render_stream_kernel<true>" in row["Name"]:
+                            rocprof_ms = {"file": os.path.relpath(path, ROOT), "avg_ms": float(row["AverageNs"]) * 1e-6}
+            except Exception:  # noqa: BLE001
+                rocprof_ms = None
+            out["config"].update({
+                "num_visible": stats.num_visible, "num_rendered": stats.num_rendered, "binned_instances": binned,
+                "frame_slots_verified_after_timed_region": verified_after,
+                # the same frame: strictly one at a time / the step's launches on one stream / camera turned every frame
+                "one_frame_in_flight_frames_per_s": one_fps,
+                "one_stream_frames_per_s": one_stream_fps,
+                "moving_camera_frames_per_s": extras.get("moving_camera", {}).get("frames_per_s"),
+            })
+            out["roofline"] = {
                 # what binds this kernel is VALU issue (valu_issue_frac below); achieved / peak / frac are the HBM figures
                 # the contract asks for (algorithmic bytes per launch over the launch's duration, against 8 TB/s)
                 "bound": "valu", "kernel": "render_stream_kernel", "achieved": ach, "peak": HBM_PEAK_GBS,
@@ -442,8 +465,8 @@ def main():
                         "cannot be recorded inside a replayed hipGraph).  The compositor is VALU/exp-bound, not "
                         "HBM-bound: saturated pixels stop reading their tile list early, so real traffic is far below "
                         "the algorithmic 40 B x num_rendered (DESIGN.md); whole-frame figures below",
-            },
-            "frame_roofline": {
+            }
+            out["frame_roofline"] = {
                 "algorithmic_bytes_per_frame": b_alg, "achieved_GBs": b_alg * fps / world / 1e9,
                 "frac_of_8TBs": b_alg * fps / world / 1e9 / HBM_PEAK_GBS,
                 "frac_of_6.3TBs": b_alg * fps / world / 1e9 / 6290.0,
@@ -452,16 +475,15 @@ def main():
                 "stage_ms_step_launches": dict(zip(PROFILE_STAGES, stage_ms_step)),
                 "single_frame_latency_ms": sum(stage_ms),
                 "frame_ms_p50": frame_ms_p50, "frame_ms_p95": frame_ms_p95,  # one frame at a time, HIP events
-            },
-        }
-        if args.breakdown:
-            print("[bench] stage ms (one frame per launch):", dict(zip(PROFILE_STAGES, stage_ms)), file=sys.stderr)
-            print(f"[bench] stage ms ({B} frames per launch):", dict(zip(PROFILE_STAGES, stage_ms_step)), file=sys.stderr)
-        out.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(raw, cam_cpu, args.cpu_frames)
-            if not args.no_extras:
-                out["cpu_baseline_config0"] = cpu_baseline_config0()
+            }
+            if args.breakdown:
+                print("[bench] stage ms (one frame per launch):", dict(zip(PROFILE_STAGES, stage_ms)), file=sys.stderr)
+                print(f"[bench] stage ms ({B} frames per launch):", dict(zip(PROFILE_STAGES, stage_ms_step)), file=sys.stderr)
+            out.update(extras)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(raw, cam_cpu, args.cpu_frames)
+                if not args.no_extras:
+                    out["cpu_baseline_config0"] = cpu_baseline_config0()
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -10,7 +10,7 @@ stats() {  # stats <name> <python script> [args...]: rocprofv3 --kernel-trace --
   f=$(find "$OUT/tmp_$name" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT/kernel_stats_$name.csv"
   rm -rf "$OUT/tmp_$name"; echo "== $name"; head -12 "$OUT/kernel_stats_$name.csv" | cut -d, -f1-4 | cut -c1-150
 }
-echo "== bench (default invocation)"; timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
+echo "== bench (default invocation)"; timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
 stats bench_one_frame_in_flight bench.py --steps 100 --warmup 10 --no-graph --no-cpu-baseline --no-extras --in-flight 1
 stats bench_three_frames_in_flight bench.py --steps 100 --warmup 10 --no-graph --no-cpu-baseline --no-extras --in-flight 3
 stats default_mode_frame tools/prof_scene.py --view sensor --default-mode

@@ -14,7 +14,7 @@ stats() {  # stats <name> <python script> [args...]: rocprofv3 --kernel-trace --
   rm -rf "$OUT/tmp_$name"; echo "== $name"; head -12 "$OUT/kernel_stats_$name.csv" | cut -d, -f1-4 | cut -c1-150
 }
 if has bench; then
-  echo "== bench (default invocation)"; timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
+  echo "== bench (default invocation)"; timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
   python - <<'PY'
 import json
 d = json.loads(open('gpurun_out/round4/bench_default.json').read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ stats() {  # stats <name> <python script> [args...]: rocprofv3 --kernel-trace --
   rm -rf "$OUT/tmp_$name"; echo "== $name"; python tools/show_stats.py "$OUT/kernel_stats_$name.csv" 13
 }
 if has bench; then
-  echo "== bench (default invocation)"; ( time timeout 1200 python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -4 $OUT/bench_default.err
+  echo "== bench (default invocation)"; ( time timeout 1200 python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -4 $OUT/bench_default.err
   echo "== bench (the driver's flags)"; timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err
   python - <<'PY'
 import json

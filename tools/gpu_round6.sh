@@ -132,7 +132,7 @@ headline_v)  # the headline on every variant library
     [ -f "$lib" ] || continue
     name=$(basename $lib .so); name=${name#libgsr_hip.}
     cp $lib gsworld_amd/libgsr_hip.so
-    timeout 600 python bench.py --no-extras --no-cpu-baseline 2> /dev/null | python -c "
+    timeout 600 python bench.py --full --no-extras --no-cpu-baseline 2> /dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['config']
 print('$name', 'value', round(d['value']), 'one frame', round(c.get('one_frame_in_flight_frames_per_s') or 0), 'one stream', round(c.get('one_stream_frames_per_s') or 0), 'p50', d['frame_roofline'].get('frame_ms_p50'), 'compositor us per 8-frame launch', round(1e3 * d['roofline']['kernel_ms'], 1), 'one frame', round(1e3 * d['roofline']['one_frame_per_launch']['kernel_ms'], 1))" | tee -a $OUT/headline_variants.txt
@@ -142,14 +142,14 @@ print('$name', 'value', round(d['value']), 'one frame', round(c.get('one_frame_i
 headline)
   for tree in . .r5ref; do
     [ -d $tree ] || continue
-    (cd $tree && timeout 600 python bench.py --no-extras --no-cpu-baseline 2> /dev/null | python -c "
+    (cd $tree && timeout 600 python bench.py $([ "$tree" = . ] && echo --full) --no-extras --no-cpu-baseline 2> /dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['config']
 print('$tree', 'value', round(d['value']), 'one frame', round(c.get('one_frame_in_flight_frames_per_s') or 0), 'one stream', round(c.get('one_stream_frames_per_s') or 0), 'p50', d['frame_roofline'].get('frame_ms_p50'))")
   done
   ;;
 bench)
-  echo "== bench (default invocation)"; ( time timeout 1500 python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -4 $OUT/bench_default.err
+  echo "== bench (default invocation)"; ( time timeout 1500 python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -4 $OUT/bench_default.err
   echo "== bench (the driver's flags)"; timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err
   python tools/show_bench.py $OUT/bench_default.json $OUT/bench_driver_flags.json
   ;;
