@@ -581,3 +581,121 @@ def mark_visible(means3D, viewmatrix, projmatrix):
             check(lib().gsr_mark_visible(P, _ptr(m3), _ptr(vm), C.c_float(NEAR_PLANE), C.c_void_p(present.data_ptr()),
                                          _stream(dev)))
     return present
+
+
+# ---- the optimizer step and the densification statistics (include/gsr.h gsr_adam_update / gsr_densification_stats) ----
+def _dense_f32(t, what: str, numel: int, dev=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{what} must be a tensor")
+    _require_gpu(t, what)
+    if dev is not None and t.device != dev:
+        raise RuntimeError(f"{what} is on {t.device}, the other tensors of the call on {dev}")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise RuntimeError(f"{what} must be a contiguous float32 tensor")
+    if t.numel() != numel:
+        raise RuntimeError(f"{what} has {t.numel()} elements, {numel} expected")
+    return t
+
+
+def _visible_arg(visible, N: int, dev):
+    """-> (tensor kept alive | None, GSR_VISIBLE_* kind) of a ``visible`` argument: None, a bool / uint8 mask or int32 radii."""
+    if visible is None:
+        return None, _lib.VISIBLE_ALL
+    if not isinstance(visible, torch.Tensor) or visible.dtype not in (torch.bool, torch.uint8, torch.int32):
+        raise RuntimeError("visible must be None, a bool / uint8 mask or the int32 radii tensor")
+    _require_gpu(visible, "visible")
+    if visible.device != dev or visible.numel() != N:
+        raise RuntimeError(f"visible must hold {N} values on {dev}")
+    return visible.contiguous(), (_lib.VISIBLE_RADII if visible.dtype == torch.int32 else _lib.VISIBLE_MASK8)
+
+
+def _use_ext(binding: str, name: str) -> bool:
+    if binding == "auto":
+        return _ext is not None and hasattr(_ext, name)
+    if binding == "ext":
+        if _ext is None or not hasattr(_ext, name):
+            raise RuntimeError(f"the compiled binding (gsworld_amd._C_ext) with {name} is not built")
+        return True
+    if binding != "ctypes":
+        raise ValueError(f"binding must be 'auto', 'ext' or 'ctypes', got {binding!r}")
+    return False
+
+
+def adam_update_groups(groups, visible, N: int, binding: str = "auto") -> None:
+    """One ``gsr_adam_update`` launch for every group of an optimizer step (include/gsr.h holds the definition): Adam without
+    bias correction on the Gaussians ``visible`` marks -- None (all), a bool / uint8 ``(N,)`` mask or the int32 ``radii`` of the
+    forward (> 0) --; the others keep parameter and moments bit for bit.  ``groups``: 1 .. 8 dicts with ``param``, ``grad``,
+    ``exp_avg``, ``exp_avg_sq`` (``N * M`` float32 each; a non-contiguous grad is made contiguous, the others must be),
+    ``lr``, ``eps`` and optionally ``beta1`` / ``beta2`` (0.9 / 0.999) and ``M`` (else ``param.numel() // N``).  Enqueued on
+    the current stream, no synchronisation.  ``binding``: "auto" (the compiled one when built), "ext" or "ctypes"."""
+    N = int(N)
+    if not 1 <= len(groups) <= _lib.ADAM_MAX_GROUPS:
+        raise RuntimeError(f"adam_update_groups: 1 .. {_lib.ADAM_MAX_GROUPS} groups per call, got {len(groups)}")
+    if N < 0:
+        raise RuntimeError(f"adam_update_groups: N = {N}")
+    dev = None
+    vals, keep = [], []
+    for k, g in enumerate(groups):
+        p = g["param"]
+        if isinstance(p, torch.Tensor):
+            _require_gpu(p, f"group {k}: param")
+            dev = p.device if dev is None else dev
+        M = int(g["M"]) if g.get("M") is not None else (p.numel() // N if N else 1)
+        if not 1 <= M <= _lib.ADAM_MAX_M:
+            raise RuntimeError(f"group {k}: M = {M} floats per Gaussian (1 .. {_lib.ADAM_MAX_M})")
+        p = _dense_f32(p, f"group {k}: param", N * M, dev)
+        m = _dense_f32(g["exp_avg"], f"group {k}: exp_avg", N * M, dev)
+        v = _dense_f32(g["exp_avg_sq"], f"group {k}: exp_avg_sq", N * M, dev)
+        grad = g["grad"]
+        if isinstance(grad, torch.Tensor) and grad.is_cuda and not grad.is_contiguous():
+            grad = grad.contiguous()
+        grad = _dense_f32(grad, f"group {k}: grad", N * M, dev)
+        keep.append(grad)
+        vals.append((p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), M, float(g["lr"]),
+                     float(g.get("beta1", 0.9)), float(g.get("beta2", 0.999)), float(g["eps"])))
+    vis, kind = _visible_arg(visible, N, dev)
+    if N == 0:
+        return
+    vptr = vis.data_ptr() if vis is not None else 0
+    if _use_ext(binding, "adam_update"):
+        _ext.adam_update(dev.index if dev.index is not None else torch.cuda.current_device(), N, vptr, kind, vals)
+        return
+    s = _lib.GsrAdamStep()
+    s.struct_size, s.N, s.num_groups, s.visible_kind, s.visible = C.sizeof(_lib.GsrAdamStep), N, len(vals), kind, vptr or None
+    for k, t in enumerate(vals):
+        s.groups[k] = _lib.GsrAdamGroup(*t)
+    with torch.cuda.device(dev):
+        check(lib().gsr_adam_update(C.byref(s), _stream(dev)))
+
+
+def adamUpdate(param, param_grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M):
+    """Upstream's ``_C.adamUpdate`` (the ``3dgs_accel`` rasterizer's sparse Adam), positional signature kept: one group of
+    ``N`` Gaussians x ``M`` floats through :func:`adam_update_groups`."""
+    adam_update_groups([{"param": param, "grad": param_grad, "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq, "lr": lr,
+                         "beta1": b1, "beta2": b2, "eps": eps, "M": M}], visible, N)
+
+
+def densification_stats(radii, grad_means2D, grad_accum, denom, max_radii2D=None, binding: str = "auto") -> None:
+    """``gsr_densification_stats`` (include/gsr.h): for every Gaussian with ``radii > 0``, ``grad_accum += |grad_means2D[:, :2]|``,
+    ``denom += 1`` and, when given, ``max_radii2D = max(max_radii2D, radii)`` -- in place, on the current stream, without the
+    compaction and the host read of ``(radii > 0).nonzero()``.  ``radii`` int32 ``(N,)``; ``grad_means2D`` float32 ``(N, 3)``
+    (made contiguous if it is not); the accumulators contiguous float32 with ``N`` elements."""
+    if not isinstance(radii, torch.Tensor) or radii.dtype != torch.int32:
+        raise RuntimeError("radii must be an int32 tensor")
+    _require_gpu(radii, "radii")
+    dev, N = radii.device, radii.numel()
+    radii = radii.contiguous()
+    if isinstance(grad_means2D, torch.Tensor) and grad_means2D.is_cuda:
+        grad_means2D = grad_means2D.contiguous()
+    g = _dense_f32(grad_means2D, "grad_means2D", 3 * N, dev)
+    acc = _dense_f32(grad_accum, "grad_accum", N, dev)
+    den = _dense_f32(denom, "denom", N, dev)
+    mx = _dense_f32(max_radii2D, "max_radii2D", N, dev) if max_radii2D is not None else None
+    if N == 0:
+        return
+    ptrs = (radii.data_ptr(), g.data_ptr(), acc.data_ptr(), den.data_ptr(), mx.data_ptr() if mx is not None else 0)
+    if _use_ext(binding, "densification_stats"):
+        _ext.densification_stats(dev.index if dev.index is not None else torch.cuda.current_device(), N, *ptrs)
+        return
+    with torch.cuda.device(dev):
+        check(lib().gsr_densification_stats(N, *(C.c_void_p(p or None) for p in ptrs), _stream(dev)))

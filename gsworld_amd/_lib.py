@@ -164,6 +164,22 @@ class GsrSensorCameras(C.Structure):
                 ("scale_sim2real", C.c_double)]
 
 
+ADAM_MAX_GROUPS, ADAM_MAX_M = 8, 4096  # include/gsr.h GSR_ADAM_MAX_GROUPS, the M limit of a group
+VISIBLE_ALL, VISIBLE_MASK8, VISIBLE_RADII = 0, 1, 2  # include/gsr.h GSR_VISIBLE_*
+
+
+class GsrAdamGroup(C.Structure):
+    """One parameter tensor of ``gsr_adam_update`` (include/gsr.h)."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("M", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
+
+
+class GsrAdamStep(C.Structure):
+    """The arguments of ``gsr_adam_update`` (include/gsr.h): every parameter group of an optimizer step."""
+    _fields_ = [("struct_size", C.c_int32), ("N", C.c_int32), ("num_groups", C.c_int32), ("visible_kind", C.c_int32),
+                ("visible", C.c_void_p), ("groups", GsrAdamGroup * ADAM_MAX_GROUPS)]
+
+
 class GsrProfile(C.Structure):
     _fields_ = [("frames", C.c_int32), ("stage_ms", C.c_double * 5)]
 
@@ -240,6 +256,10 @@ def lib() -> C.CDLL:
     L.gsr_pointcloud_workspace.argtypes = [C.POINTER(GsrCloudSpec), C.POINTER(C.c_int64)]
     L.gsr_cameras_from_extrinsics.restype = C.c_int
     L.gsr_cameras_from_extrinsics.argtypes = [C.POINTER(GsrSensorCameras), C.c_void_p]
+    L.gsr_adam_update.restype = C.c_int
+    L.gsr_adam_update.argtypes = [C.POINTER(GsrAdamStep), C.c_void_p]
+    L.gsr_densification_stats.restype = C.c_int
+    L.gsr_densification_stats.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gsr_profile_enable.restype = C.c_int
     L.gsr_profile_enable.argtypes = [C.c_int]
     L.gsr_profile_collect.restype = C.c_int

@@ -655,6 +655,50 @@ torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &vi
     return present;
 }
 
+// ---- the optimizer step and the densification statistics (gsworld_amd._C.adam_update_groups / densification_stats) -----
+// Buffers travel as device addresses (0 = NULL); gsworld_amd/_C.py has checked dtype, device and layout.  `groups`: tuples
+// (param, grad, exp_avg, exp_avg_sq, M, lr, beta1, beta2, eps).
+void adam_update(int64_t device_index, int64_t N, int64_t visible, int64_t visible_kind, const py::list &groups) {
+    TORCH_CHECK(groups.size() >= 1 && groups.size() <= GSR_ADAM_MAX_GROUPS, "adam_update: 1 .. ", GSR_ADAM_MAX_GROUPS,
+                " groups, got ", groups.size());
+    auto P = [](const py::handle &h) { return reinterpret_cast<float *>((uintptr_t)h.cast<int64_t>()); };
+    GsrAdamStep s;
+    std::memset(&s, 0, sizeof(s));
+    s.struct_size = (int32_t)sizeof(GsrAdamStep);
+    s.N = (int32_t)N;
+    s.num_groups = (int32_t)groups.size();
+    s.visible_kind = (int32_t)visible_kind;
+    s.visible = reinterpret_cast<const void *>((uintptr_t)visible);
+    for (size_t k = 0; k < groups.size(); k++) {
+        const py::tuple t = groups[k].cast<py::tuple>();
+        TORCH_CHECK(t.size() == 9, "adam_update: a group is a tuple of 9 values, got ", t.size());
+        GsrAdamGroup &g = s.groups[k];
+        g.param = P(t[0]);
+        g.grad = P(t[1]);
+        g.exp_avg = P(t[2]);
+        g.exp_avg_sq = P(t[3]);
+        g.M = t[4].cast<int32_t>();
+        g.lr = (float)t[5].cast<double>();
+        g.beta1 = (float)t[6].cast<double>();
+        g.beta2 = (float)t[7].cast<double>();
+        g.eps = (float)t[8].cast<double>();
+    }
+    const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int rc = gsr_adam_update(&s, current_stream(dev));
+    TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+}
+
+void densification_stats(int64_t device_index, int64_t N, int64_t radii, int64_t grad_means2D, int64_t grad_accum,
+                         int64_t denom, int64_t max_radii2D) {
+    const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    auto F = [](int64_t a) { return reinterpret_cast<float *>((uintptr_t)a); };
+    const int rc = gsr_densification_stats((int32_t)N, reinterpret_cast<const int32_t *>((uintptr_t)radii), F(grad_means2D),
+                                           F(grad_accum), F(denom), F(max_radii2D), current_stream(dev));
+    TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -700,5 +744,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("frame_stats", &frame_stats);
     m.def("render_maps", &render_maps);
     py::class_<CloudPack>(m, "CloudPack").def(py::init<const py::tuple &>()).def("run", &CloudPack::run);
+    m.def("adam_update", &adam_update);
+    m.def("densification_stats", &densification_stats);
     m.def("version", []() { return std::string(gsr_version()); });
 }

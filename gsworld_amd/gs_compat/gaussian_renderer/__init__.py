@@ -159,7 +159,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             dir_pp_normalized = dir_pp / dir_pp.norm(dim=1, keepdim=True)
             colors_precomp = torch.clamp_min(eval_sh(pc.active_sh_degree, shs_view, dir_pp_normalized) + 0.5, 0.0)
         else:
-            # separate_sh (3dgs_accel signature) is never requested: SparseGaussianAdam is not exported
+            # separate_sh (3dgs_accel signature) is never requested: the drop-in package does not export
+            # SparseGaussianAdam (it lives in gsworld_amd.optim)
             shs = pc.get_features
     else:
         colors_precomp = override_color
@@ -236,10 +237,8 @@ def _finish(rendered_image, radii, depth_image, screenspace_points, viewpoint_ca
         return _LazyResult({"render": rendered_image, "radii": radii, "depth": depth_image},
                            {"viewspace_points": screenspace_points,
                             "visibility_filter": lambda: (radii > 0).nonzero()})
-    return {
-        "render": rendered_image,
-        "viewspace_points": screenspace_points,
-        "visibility_filter": (radii > 0).nonzero(),
-        "radii": radii,
-        "depth": depth_image,
-    }
+    # (a training loop that hands `radii` to add_densification_stats / SparseGaussianAdam.step never reads the filter: the
+    #  iteration then runs without a host read)
+    return _LazyResult({"render": rendered_image, "viewspace_points": screenspace_points, "radii": radii,
+                        "depth": depth_image},
+                       {"visibility_filter": lambda: (radii > 0).nonzero()})

@@ -154,7 +154,29 @@ class GaussianModel:
             {"params": [self._scaling], "lr": training_args.scaling_lr, "name": "scaling"},
             {"params": [self._rotation], "lr": training_args.rotation_lr, "name": "rotation"},
         ]
-        self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        if self.optimizer_type == "sparse_adam":
+            # upstream: `from diff_gaussian_rasterization import SparseGaussianAdam`; here it lives in gsworld_amd.optim
+            from gsworld_amd.optim import SparseGaussianAdam
+
+            self.optimizer = SparseGaussianAdam(groups, lr=0.0, eps=1e-15)
+        else:
+            self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter):
+        """upstream's bookkeeping of an iteration.  ``update_filter`` = the int32 ``radii`` of the frame: one fused launch
+        that reads them on the device (no ``nonzero``, no host read; ``max_radii2D`` is updated in the same pass); a mask
+        or index tensor: upstream's two lines."""
+        if update_filter.dtype == torch.int32:
+            from gsworld_amd.optim import densification_stats
+
+            if self.max_radii2D.numel() != update_filter.numel():
+                self.max_radii2D = torch.zeros((update_filter.numel(),), device=update_filter.device)
+            densification_stats(update_filter, viewspace_point_tensor.grad, self.xyz_gradient_accum, self.denom,
+                                self.max_radii2D)
+            return
+        self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1,
+                                                             keepdim=True)
+        self.denom[update_filter] += 1
 
     def _swap_group_tensor(self, group, new_tensor, state_map):
         old = group["params"][0]

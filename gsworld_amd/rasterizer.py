@@ -5,8 +5,9 @@ Mirrors the un-vendored upstream ``diff_gaussian_rasterization/__init__.py`` tha
 /root/reference/gsworld/mani_skill/utils/wrappers/gs_world_wrapper.py:266-267): same class and field names,
 same argument meaning, same exceptions, same return tuple ``(color, radii, invdepth)``.
 
-``SparseGaussianAdam`` is deliberately NOT exported: GSWorld probes for it
-(gs_world_wrapper.py:22-26) and its absence selects the ``separate_sh=False`` call path.
+``SparseGaussianAdam`` is deliberately NOT exported HERE: GSWorld probes this package for it
+(gs_world_wrapper.py:22-26) and its absence selects the ``separate_sh=False`` call path.  The optimizer lives in
+:mod:`gsworld_amd.optim`; a training script imports it from there.
 """
 from __future__ import annotations
 

@@ -594,6 +594,66 @@ typedef struct GsrSensorCameras {
 } GsrSensorCameras;
 int gsr_cameras_from_extrinsics(const GsrSensorCameras *spec, void *stream);
 
+/*
+ * The optimizer step of a training iteration (optim.hip): Adam on the Gaussians a frame saw, for up to
+ * GSR_ADAM_MAX_GROUPS parameter tensors in ONE launch.  This comment is the definition.  Group k holds N Gaussians of M
+ * floats each: param, grad, exp_avg (m), exp_avg_sq (v), all (N, M) contiguous float32 on the device.  For every element
+ * of a VISIBLE Gaussian, in binary32, every operation rounded once, nothing contracted, (1 - beta) formed once in
+ * binary32 on the host:
+ *     m' = (beta1 * m) + ((1 - beta1) * g)
+ *     v' = (beta2 * v) + (((1 - beta2) * g) * g)
+ *     p' = p + (((-lr) * m') / (sqrtf(v') + eps))
+ * with `/` and sqrtf the correctly rounded ones and denormals kept; m', v', p' are stored.  There is no bias correction
+ * and no step counter (the 3DGS sparse optimizer's semantics).  A non-finite gradient of a visible Gaussian propagates
+ * as the arithmetic says.  An INVISIBLE Gaussian's param, exp_avg and exp_avg_sq keep their bits -- its moments do not
+ * decay: this is not dense Adam -- and its grad is never read (it may hold anything, NaN included).  Visibility is per
+ * Gaussian and shared by the groups: `visible` NULL with GSR_VISIBLE_ALL, N uint8 / bool with GSR_VISIBLE_MASK8 (!= 0),
+ * N int32 with GSR_VISIBLE_RADII (> 0: the `radii` a forward wrote, as they are).
+ * Pointers need only be 4-byte aligned: a group whose four arrays are all 16-byte aligned is walked in 16-byte vectors
+ * (one that straddles Gaussians of different visibility updates exactly the visible one's elements), any other group
+ * element by element; the result is the same.  Element indices are 64-bit.  One launch on `stream`, no allocation, no
+ * synchronisation: the call can be captured into a hipGraph, and a replay repeats the captured lr.
+ * N == 0 returns GSR_OK without touching the device.  GSR_E_INVALID: struct_size, N < 0, num_groups outside
+ * 1..GSR_ADAM_MAX_GROUPS, an M outside 1..4096, a null pointer in a used group when N > 0, an unknown visible_kind, a
+ * kind that does not match `visible` being NULL or not.
+ */
+#define GSR_ADAM_MAX_GROUPS 8
+#define GSR_VISIBLE_ALL 0   /* visible == NULL: every Gaussian */
+#define GSR_VISIBLE_MASK8 1 /* uint8 / bool (N): != 0 */
+#define GSR_VISIBLE_RADII 2 /* int32 (N): > 0 -- the forward's radii as they are */
+typedef struct GsrAdamGroup {
+    float *param;                /* (N, M) contiguous float32, device -- as are the next three */
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int32_t M;                   /* floats per Gaussian, 1 <= M <= 4096 */
+    float lr, beta1, beta2, eps; /* [host] */
+} GsrAdamGroup;
+typedef struct GsrAdamStep {
+    int32_t struct_size;         /* sizeof(GsrAdamStep): the library rejects a mismatch (GSR_E_INVALID) */
+    int32_t N;                   /* Gaussians */
+    int32_t num_groups;          /* groups[0 .. num_groups) are used */
+    int32_t visible_kind;        /* GSR_VISIBLE_* */
+    const void *visible;
+    GsrAdamGroup groups[GSR_ADAM_MAX_GROUPS];
+} GsrAdamStep;
+int gsr_adam_update(const GsrAdamStep *step, void *stream);
+
+/*
+ * The densification statistics of a training iteration (optim.hip), upstream's `max_radii2D[vis] = max(...)` and
+ * `add_densification_stats` without the compaction and host read of `(radii > 0).nonzero()`.  For every Gaussian with
+ * radii[i] > 0 -- the others are untouched --, with (gx, gy) = grad_means2D[3 i], grad_means2D[3 i + 1] (the third column
+ * is never read), in binary32, every operation rounded once:
+ *     grad_accum[i]  = grad_accum[i] + sqrtf((gx * gx) + (gy * gy))
+ *     denom[i]       = denom[i] + 1
+ *     max_radii2D[i] = fmaxf(max_radii2D[i], (float)radii[i])          (when max_radii2D is not NULL)
+ * One launch on `stream`, no allocation, no synchronisation (capturable).  N == 0 returns GSR_OK without touching the
+ * device; GSR_E_INVALID: N < 0, or a null radii / grad_means2D / grad_accum / denom when N > 0.
+ */
+int gsr_densification_stats(int32_t N, const int32_t *radii, const float *grad_means2D /* (N,3) */,
+                            float *grad_accum /* (N) */, float *denom /* (N) */,
+                            float *max_radii2D /* (N) or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
