@@ -699,3 +699,119 @@ def densification_stats(radii, grad_means2D, grad_accum, denom, max_radii2D=None
         return
     with torch.cuda.device(dev):
         check(lib().gsr_densification_stats(N, *(C.c_void_p(p or None) for p in ptrs), _stream(dev)))
+
+
+# ---- densify-and-prune (include/gsr.h gsr_densify_plan / gsr_densify_apply) -------------------------------------------
+def densify_workspace_bytes(N: int) -> int:
+    """``gsr_densify_workspace_bytes``: the workspace ``densify_plan`` fills for ``densify_apply`` (a multiple of 256)."""
+    return int(lib().gsr_densify_workspace_bytes(int(N)))
+
+
+def densify_plan(grad_accum, denom, scaling, opacity, *, grad_threshold, min_opacity, dense_limit, world_limit,
+                 prune_world_size, counts=None, workspace=None, binding: str = "auto"):
+    """``gsr_densify_plan`` (include/gsr.h holds the definition): the decisions of upstream's ``densify_and_prune`` for every
+    Gaussian -- kept, cloned, split into two children, pruned -- from the accumulated statistics and the raw ``scaling`` (N, 3)
+    and ``opacity`` (N elements).  -> ``(counts, workspace)``: ``counts`` int32 (4,) on the device (kept, clones, split, N_out),
+    ``workspace`` the uint8 tensor ``densify_apply`` reads; both are allocated when not given.  The four scalars are passed as
+    binary32 values.  Three launches on the current stream, no synchronisation; N = 0 launches nothing (counts is zeroed)."""
+    if not isinstance(scaling, torch.Tensor):
+        raise RuntimeError("scaling must be a tensor")
+    _require_gpu(scaling, "scaling")
+    dev = scaling.device
+    N = scaling.numel() // 3
+    if N > _lib.DENSIFY_MAX_N:
+        raise RuntimeError(f"densify_plan: N = {N} exceeds 2^30")
+    sc = _dense_f32(scaling, "scaling", 3 * N, dev)
+    acc = _dense_f32(grad_accum, "grad_accum", N, dev)
+    den = _dense_f32(denom, "denom", N, dev)
+    op = _dense_f32(opacity, "opacity", N, dev)
+    nbytes = densify_workspace_bytes(N)
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.uint8
+          or not workspace.is_contiguous() or workspace.numel() < nbytes):
+        raise RuntimeError(f"workspace must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}")
+    if counts is None:
+        counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    elif (not isinstance(counts, torch.Tensor) or counts.device != dev or counts.dtype != torch.int32
+          or not counts.is_contiguous() or counts.numel() != 4):
+        raise RuntimeError(f"counts must be a contiguous int32 tensor of 4 elements on {dev}")
+    if N == 0:
+        counts.zero_()
+        return counts, workspace
+    thr, mop, dl, wl = (float(np.float32(x)) for x in (grad_threshold, min_opacity, dense_limit, world_limit))
+    if _use_ext(binding, "densify_plan"):
+        _ext.densify_plan(dev.index if dev.index is not None else torch.cuda.current_device(), N, acc.data_ptr(),
+                          den.data_ptr(), sc.data_ptr(), op.data_ptr(), thr, mop, dl, wl, bool(prune_world_size),
+                          counts.data_ptr(), workspace.data_ptr(), workspace.numel())
+        return counts, workspace
+    s = _lib.GsrDensifyPlan()
+    s.struct_size, s.N = C.sizeof(_lib.GsrDensifyPlan), N
+    s.grad_accum, s.denom, s.scaling, s.opacity = acc.data_ptr(), den.data_ptr(), sc.data_ptr(), op.data_ptr()
+    s.grad_threshold, s.min_opacity, s.dense_limit, s.world_limit = thr, mop, dl, wl
+    s.prune_world_size = int(bool(prune_world_size))
+    s.counts, s.workspace, s.workspace_bytes = counts.data_ptr(), workspace.data_ptr(), workspace.numel()
+    with torch.cuda.device(dev):
+        check(lib().gsr_densify_plan(C.byref(s), _stream(dev)))
+    return counts, workspace
+
+
+DENSIFY_ROLES = {"copy": _lib.DENSIFY_COPY, "xyz": _lib.DENSIFY_XYZ, "scaling": _lib.DENSIFY_SCALING}
+
+
+def densify_apply(N: int, N_out: int, workspace, xyz, scaling, rotation, noise, groups, parent,
+                  binding: str = "auto") -> None:
+    """``gsr_densify_apply`` (include/gsr.h): ONE launch that writes the ``N_out`` output rows of every group -- kept rows with
+    their moments, clones and children with zero moments, children of the ``"xyz"`` / ``"scaling"`` roles computed -- and
+    ``parent`` (int32, ``N_out``).  ``groups``: up to 8 dicts with ``src`` and ``dst``, each ``(param, exp_avg, exp_avg_sq)``
+    with both moments None for a group without state, and optionally ``M`` and ``role`` ("copy", "xyz", "scaling").  ``N``,
+    ``workspace``: the plan's; ``N_out``: what the caller read from the plan's ``counts[3]``; ``noise`` (N, 2, 3) standard
+    normals indexed by parent.  Enqueued on the current stream, no synchronisation."""
+    N, N_out = int(N), int(N_out)
+    if len(groups) > _lib.ADAM_MAX_GROUPS:
+        raise RuntimeError(f"densify_apply: at most {_lib.ADAM_MAX_GROUPS} groups per call, got {len(groups)}")
+    if not 0 <= N <= _lib.DENSIFY_MAX_N or not 0 <= N_out <= 2 * N:
+        raise RuntimeError(f"densify_apply: N = {N}, N_out = {N_out}")
+    if not isinstance(xyz, torch.Tensor):
+        raise RuntimeError("xyz must be a tensor")
+    _require_gpu(xyz, "xyz")
+    dev = xyz.device
+    x = _dense_f32(xyz, "xyz", 3 * N, dev)
+    sc = _dense_f32(scaling, "scaling", 3 * N, dev)
+    rot = _dense_f32(rotation, "rotation", 4 * N, dev)
+    nz = _dense_f32(noise, "noise", 6 * N, dev)
+    if (not isinstance(parent, torch.Tensor) or parent.device != dev or parent.dtype != torch.int32
+            or not parent.is_contiguous() or parent.numel() != N_out):
+        raise RuntimeError(f"parent must be a contiguous int32 tensor of {N_out} elements on {dev}")
+    if (not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.uint8
+            or not workspace.is_contiguous()):
+        raise RuntimeError(f"workspace must be the contiguous uint8 tensor of densify_plan on {dev}")
+    vals = []
+    for k, g in enumerate(groups):
+        sp = g["src"][0]
+        M = int(g["M"]) if g.get("M") is not None else (sp.numel() // N if N else 1)
+        if not 1 <= M <= _lib.ADAM_MAX_M:
+            raise RuntimeError(f"group {k}: M = {M} floats per Gaussian (1 .. {_lib.ADAM_MAX_M})")
+        moments = g["src"][1] is not None
+        if any((t is not None) != moments for t in (g["src"][2], g["dst"][1], g["dst"][2])):
+            raise RuntimeError(f"group {k}: exp_avg, exp_avg_sq and their outputs are all given or all None")
+        ptrs = []
+        for side, rows in (("src", N), ("dst", N_out)):
+            for name, t in zip(("param", "exp_avg", "exp_avg_sq"), g[side]):
+                ptrs.append(0 if t is None else _dense_f32(t, f"group {k}: {side} {name}", rows * M, dev).data_ptr())
+        vals.append((*ptrs, M, DENSIFY_ROLES[g.get("role", "copy")]))
+    if N == 0 or N_out == 0:
+        return
+    if _use_ext(binding, "densify_apply"):
+        _ext.densify_apply(dev.index if dev.index is not None else torch.cuda.current_device(), N, N_out,
+                           workspace.data_ptr(), workspace.numel(), x.data_ptr(), sc.data_ptr(), rot.data_ptr(),
+                           nz.data_ptr(), parent.data_ptr(), vals)
+        return
+    s = _lib.GsrDensifyApply()
+    s.struct_size, s.N, s.N_out, s.num_groups = C.sizeof(_lib.GsrDensifyApply), N, N_out, len(vals)
+    s.workspace, s.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    s.xyz, s.scaling, s.rotation, s.noise, s.parent = x.data_ptr(), sc.data_ptr(), rot.data_ptr(), nz.data_ptr(), parent.data_ptr()
+    for k, t in enumerate(vals):
+        s.groups[k] = _lib.GsrDensifyGroup(*(v or None for v in t[:6]), t[6], t[7])
+    with torch.cuda.device(dev):
+        check(lib().gsr_densify_apply(C.byref(s), _stream(dev)))

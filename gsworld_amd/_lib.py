@@ -180,6 +180,32 @@ class GsrAdamStep(C.Structure):
                 ("visible", C.c_void_p), ("groups", GsrAdamGroup * ADAM_MAX_GROUPS)]
 
 
+DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2  # include/gsr.h GSR_DENSIFY_*: a group's role in gsr_densify_apply
+DENSIFY_MAX_N = 1 << 30
+
+
+class GsrDensifyPlan(C.Structure):
+    """The arguments of ``gsr_densify_plan`` (include/gsr.h): the decisions of a densify-and-prune."""
+    _fields_ = [("struct_size", C.c_int32), ("N", C.c_int32), ("grad_accum", C.c_void_p), ("denom", C.c_void_p),
+                ("scaling", C.c_void_p), ("opacity", C.c_void_p), ("grad_threshold", C.c_float), ("min_opacity", C.c_float),
+                ("dense_limit", C.c_float), ("world_limit", C.c_float), ("prune_world_size", C.c_int32),
+                ("reserved", C.c_int32), ("counts", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class GsrDensifyGroup(C.Structure):
+    """One parameter tensor of ``gsr_densify_apply`` (include/gsr.h): sources (N, M), destinations (N_out, M)."""
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("out_param", C.c_void_p),
+                ("out_exp_avg", C.c_void_p), ("out_exp_avg_sq", C.c_void_p), ("M", C.c_int32), ("role", C.c_int32)]
+
+
+class GsrDensifyApply(C.Structure):
+    """The arguments of ``gsr_densify_apply`` (include/gsr.h): the data movement of a densify-and-prune."""
+    _fields_ = [("struct_size", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("num_groups", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("xyz", C.c_void_p), ("scaling", C.c_void_p),
+                ("rotation", C.c_void_p), ("noise", C.c_void_p), ("parent", C.c_void_p),
+                ("groups", GsrDensifyGroup * ADAM_MAX_GROUPS)]
+
+
 class GsrProfile(C.Structure):
     _fields_ = [("frames", C.c_int32), ("stage_ms", C.c_double * 5)]
 
@@ -260,6 +286,12 @@ def lib() -> C.CDLL:
     L.gsr_adam_update.argtypes = [C.POINTER(GsrAdamStep), C.c_void_p]
     L.gsr_densification_stats.restype = C.c_int
     L.gsr_densification_stats.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gsr_densify_workspace_bytes.restype = C.c_int64
+    L.gsr_densify_workspace_bytes.argtypes = [C.c_int32]
+    L.gsr_densify_plan.restype = C.c_int
+    L.gsr_densify_plan.argtypes = [C.POINTER(GsrDensifyPlan), C.c_void_p]
+    L.gsr_densify_apply.restype = C.c_int
+    L.gsr_densify_apply.argtypes = [C.POINTER(GsrDensifyApply), C.c_void_p]
     L.gsr_profile_enable.restype = C.c_int
     L.gsr_profile_enable.argtypes = [C.c_int]
     L.gsr_profile_collect.restype = C.c_int

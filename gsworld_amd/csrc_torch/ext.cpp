@@ -699,6 +699,72 @@ void densification_stats(int64_t device_index, int64_t N, int64_t radii, int64_t
     TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
 }
 
+// ---- densify-and-prune (gsworld_amd._C.densify_plan / densify_apply) -----------------------------------------------------
+void densify_plan(int64_t device_index, int64_t N, int64_t grad_accum, int64_t denom, int64_t scaling, int64_t opacity,
+                  double grad_threshold, double min_opacity, double dense_limit, double world_limit, bool prune_world_size,
+                  int64_t counts, int64_t workspace, int64_t workspace_bytes) {
+    auto F = [](int64_t a) { return reinterpret_cast<const float *>((uintptr_t)a); };
+    GsrDensifyPlan s;
+    std::memset(&s, 0, sizeof(s));
+    s.struct_size = (int32_t)sizeof(GsrDensifyPlan);
+    s.N = (int32_t)N;
+    s.grad_accum = F(grad_accum);
+    s.denom = F(denom);
+    s.scaling = F(scaling);
+    s.opacity = F(opacity);
+    s.grad_threshold = (float)grad_threshold;  // (the caller passes binary32 values: exact)
+    s.min_opacity = (float)min_opacity;
+    s.dense_limit = (float)dense_limit;
+    s.world_limit = (float)world_limit;
+    s.prune_world_size = prune_world_size ? 1 : 0;
+    s.counts = reinterpret_cast<int32_t *>((uintptr_t)counts);
+    s.workspace = reinterpret_cast<void *>((uintptr_t)workspace);
+    s.workspace_bytes = workspace_bytes;
+    const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int rc = gsr_densify_plan(&s, current_stream(dev));
+    TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+}
+
+// `groups`: tuples (param, exp_avg, exp_avg_sq, out_param, out_exp_avg, out_exp_avg_sq, M, role)
+void densify_apply(int64_t device_index, int64_t N, int64_t N_out, int64_t workspace, int64_t workspace_bytes, int64_t xyz,
+                   int64_t scaling, int64_t rotation, int64_t noise, int64_t parent, const py::list &groups) {
+    TORCH_CHECK(groups.size() <= GSR_ADAM_MAX_GROUPS, "densify_apply: at most ", GSR_ADAM_MAX_GROUPS, " groups, got ",
+                groups.size());
+    auto P = [](const py::handle &h) { return reinterpret_cast<float *>((uintptr_t)h.cast<int64_t>()); };
+    auto F = [](int64_t a) { return reinterpret_cast<const float *>((uintptr_t)a); };
+    GsrDensifyApply s;
+    std::memset(&s, 0, sizeof(s));
+    s.struct_size = (int32_t)sizeof(GsrDensifyApply);
+    s.N = (int32_t)N;
+    s.N_out = (int32_t)N_out;
+    s.num_groups = (int32_t)groups.size();
+    s.workspace = reinterpret_cast<const void *>((uintptr_t)workspace);
+    s.workspace_bytes = workspace_bytes;
+    s.xyz = F(xyz);
+    s.scaling = F(scaling);
+    s.rotation = F(rotation);
+    s.noise = F(noise);
+    s.parent = reinterpret_cast<int32_t *>((uintptr_t)parent);
+    for (size_t k = 0; k < groups.size(); k++) {
+        const py::tuple t = groups[k].cast<py::tuple>();
+        TORCH_CHECK(t.size() == 8, "densify_apply: a group is a tuple of 8 values, got ", t.size());
+        GsrDensifyGroup &g = s.groups[k];
+        g.param = P(t[0]);
+        g.exp_avg = P(t[1]);
+        g.exp_avg_sq = P(t[2]);
+        g.out_param = P(t[3]);
+        g.out_exp_avg = P(t[4]);
+        g.out_exp_avg_sq = P(t[5]);
+        g.M = t[6].cast<int32_t>();
+        g.role = t[7].cast<int32_t>();
+    }
+    const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int rc = gsr_densify_apply(&s, current_stream(dev));
+    TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -746,5 +812,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<CloudPack>(m, "CloudPack").def(py::init<const py::tuple &>()).def("run", &CloudPack::run);
     m.def("adam_update", &adam_update);
     m.def("densification_stats", &densification_stats);
+    m.def("densify_plan", &densify_plan);
+    m.def("densify_apply", &densify_apply);
     m.def("version", []() { return std::string(gsr_version()); });
 }

@@ -4,8 +4,10 @@ and merges (/root/reference/gsworld/utils/gaussian_merger.py:213-274).
 
 Restates the layout and activations of the 3DGS python layer: raw parameters
 ``_xyz (N,3)``, ``_features_dc (N,1,3)``, ``_features_rest (N,15,3)``, ``_scaling (N,3)`` (log), ``_rotation (N,4)``
-(r,x,y,z), ``_opacity (N,1)`` (logit); getters apply exp / normalize / sigmoid / cat.  The optimiser-side
-methods (training_setup, densification) are kept to what the subclass hooks call.
+(r,x,y,z), ``_opacity (N,1)`` (logit); getters apply exp / normalize / sigmoid / cat.  The optimiser side:
+training_setup, the two hooks subclasses override (prune_points, densification_postfix), and upstream's densify_and_prune /
+densify_and_clone / densify_and_split / reset_opacity -- fused on the device for a stock model (gsworld_amd.optim), the
+literal torch sequence through the hooks for a subclass that overrides them.
 """
 import os
 
@@ -236,6 +238,112 @@ class GaussianModel:
         self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
         self.denom = torch.zeros((n, 1), device=dev)
         self.max_radii2D = torch.zeros((n,), device=dev)
+
+    # ---- densification (every densification_interval iterations) and opacity reset ------------------------------
+    def replace_tensor_to_optimizer(self, tensor, name):
+        """-> {name: the new parameter}; both moments of the group become zeros (``step`` stays)."""
+        out = {}
+        for group in self.optimizer.param_groups:
+            if group["name"] == name:
+                out[name] = self._swap_group_tensor(group, tensor, torch.zeros_like)
+        return out
+
+    @torch.no_grad()
+    def reset_opacity(self):
+        """opacity = inverse_sigmoid(min(get_opacity, 0.01)), its moments zeroed (every opacity_reset_interval iterations)."""
+        opacities_new = self.inverse_opacity_activation(torch.min(self.get_opacity,
+                                                                  torch.ones_like(self.get_opacity) * 0.01))
+        if self.optimizer is None:
+            self._opacity = nn.Parameter(opacities_new) if isinstance(self._opacity, nn.Parameter) else opacities_new
+            return
+        self._opacity = self.replace_tensor_to_optimizer(opacities_new, "opacity")["opacity"]
+
+    def densify_and_clone(self, grads, grad_threshold, scene_extent):
+        selected = torch.norm(grads, dim=-1) >= grad_threshold
+        selected = torch.logical_and(selected,
+                                     torch.max(self.get_scaling, dim=1).values <= self.percent_dense * scene_extent)
+        tmp_radii = getattr(self, "tmp_radii", None)
+        self.densification_postfix(self._xyz[selected], self._features_dc[selected], self._features_rest[selected],
+                                   self._opacity[selected], self._scaling[selected], self._rotation[selected],
+                                   tmp_radii[selected] if tmp_radii is not None else None)
+
+    def densify_and_split(self, grads, grad_threshold, scene_extent, N=2, noise=None):
+        """``noise``: ``(n, N, 3)`` standard normals indexed by parent row (n = the rows ``grads`` covers); a child's offset
+        is ``exp(scaling) * noise`` where upstream draws ``torch.normal(0, exp(scaling))`` -- the same distribution.  A row is
+        split when it is hot and NOT small (``~(max <= limit)``, the complement of densify_and_clone's test; upstream
+        writes ``max > limit``, which differs only for a NaN scale)."""
+        from utils.general_utils import build_rotation
+
+        n_init = self.get_xyz.shape[0]
+        dev = self._xyz.device
+        padded_grad = torch.zeros((n_init,), device=dev)
+        padded_grad[:grads.shape[0]] = grads.squeeze(-1) if grads.dim() > 1 else grads
+        selected = padded_grad >= grad_threshold
+        selected = torch.logical_and(selected, torch.logical_not(
+            torch.max(self.get_scaling, dim=1).values <= self.percent_dense * scene_extent))
+        stds = self.get_scaling[selected].repeat(N, 1)
+        if noise is None:
+            samples = torch.normal(mean=torch.zeros((stds.size(0), 3), device=dev), std=stds)
+        else:
+            padded = torch.zeros((n_init, N, 3), device=dev)
+            padded[:noise.shape[0]] = noise
+            samples = stds * padded[selected].transpose(0, 1).reshape(-1, 3)
+        rots = build_rotation(self._rotation[selected]).repeat(N, 1, 1)
+        new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + self.get_xyz[selected].repeat(N, 1)
+        new_scaling = self.scaling_inverse_activation(self.get_scaling[selected].repeat(N, 1) / (0.8 * N))
+        tmp_radii = getattr(self, "tmp_radii", None)
+        self.densification_postfix(new_xyz, self._features_dc[selected].repeat(N, 1, 1),
+                                   self._features_rest[selected].repeat(N, 1, 1), self._opacity[selected].repeat(N, 1),
+                                   new_scaling, self._rotation[selected].repeat(N, 1),
+                                   tmp_radii[selected].repeat(N) if tmp_radii is not None else None)
+        prune_filter = torch.cat((selected, torch.zeros(N * int(selected.sum()), device=dev, dtype=torch.bool)))
+        self.prune_points(prune_filter)
+
+    def _fused_densify(self):
+        """The fused route is taken when the tensors are on a HIP device and the class overrides neither hook (a subclass
+        that does -- GSWorld's Semantic3DGSWrapper gives new rows zero semantics there -- goes through its hooks)."""
+        cls = type(self)
+        return (self._xyz.is_cuda and cls.prune_points is GaussianModel.prune_points
+                and cls.densification_postfix is GaussianModel.densification_postfix)
+
+    @torch.no_grad()
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, radii, noise=None):
+        """Upstream's sequence: clone the small hot Gaussians, split the large hot ones in two, prune the transparent and
+        (``if max_screen_size:``) the oversized ones; rows come out as kept | clones | first children | second children.
+
+        ``densification_postfix`` zeroes ``max_radii2D`` before the final prune reads it, so inside this sequence upstream's
+        screen-size test (``max_radii2D > max_screen_size``) selects nothing and only its world-size companion acts.  Both
+        routes reproduce that and do not repair it: the fused one (``gsworld_amd.optim.densify_and_prune``: one host read
+        instead of some forty compactions) reads neither ``max_radii2D`` nor ``radii``.  ``noise``: ``(N, 2, 3)`` standard
+        normals indexed by parent, drawn when not given.  Afterwards ``xyz_gradient_accum``, ``denom`` and ``max_radii2D``
+        are zeros of the new size and ``tmp_radii`` is None."""
+        self.last_densify_route = "fused" if self._fused_densify() else "literal"
+        if self.last_densify_route == "fused":
+            from gsworld_amd.optim import densify_and_prune
+
+            out, _, _ = densify_and_prune(self._current(), self.optimizer, self.xyz_gradient_accum, self.denom,
+                                          grad_threshold=max_grad, min_opacity=min_opacity, extent=extent,
+                                          percent_dense=self.percent_dense, prune_world_size=bool(max_screen_size),
+                                          noise=noise)
+            self._rebind(out)
+            n, dev = self._xyz.shape[0], self._xyz.device
+            self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+            self.denom = torch.zeros((n, 1), device=dev)
+            self.max_radii2D = torch.zeros((n,), device=dev)
+            self.tmp_radii = None
+            return
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        self.tmp_radii = radii
+        self.densify_and_clone(grads, max_grad, extent)
+        self.densify_and_split(grads, max_grad, extent, noise=noise)
+        prune_mask = (self.get_opacity < min_opacity).squeeze(-1)
+        if max_screen_size:
+            big_points_vs = self.max_radii2D > max_screen_size
+            big_points_ws = self.get_scaling.max(dim=1).values > 0.1 * extent
+            prune_mask = torch.logical_or(torch.logical_or(prune_mask, big_points_vs), big_points_ws)
+        self.prune_points(prune_mask)
+        self.tmp_radii = None
 
     # ---- PLY interchange (property order of SURVEY.md 8f-3) -------------------------------------------------
     def construct_list_of_attributes(self):

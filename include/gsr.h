@@ -654,6 +654,105 @@ int gsr_densification_stats(int32_t N, const int32_t *radii, const float *grad_m
                             float *grad_accum /* (N) */, float *denom /* (N) */,
                             float *max_radii2D /* (N) or NULL */, void *stream);
 
+/*
+ * Densify-and-prune of the model on the device (densify.hip): what upstream's densify_and_prune does every
+ * densification_interval iterations -- densify_and_clone, densify_and_split (N = 2), the final prune_points -- as two
+ * calls, so that the data-dependent output size crosses to the host exactly once, between them.  This comment is the
+ * definition.
+ *
+ * gsr_densify_plan decides.  Per Gaussian i < N, in binary32, every operation rounded once, nothing contracted, expf /
+ * logf the accurate (<= 1 ulp) ones, s = scaling[3 i ..] (log space), o = opacity[i] (logit):
+ *     g          = grad_accum[i] / denom[i];  a NaN g becomes 0
+ *     hot_clone  = fabsf(g) >= grad_threshold;       hot_split = g >= grad_threshold
+ *     smax       = max(max(expf(s0), expf(s1)), expf(s2)), a max that PROPAGATES NaN (torch.max, not fmaxf)
+ *     small      = smax <= dense_limit               (dense_limit = percent_dense * extent, formed by the caller)
+ *     clone_sel  = hot_clone && small;               split_sel = hot_split && !small
+ *     op         = 1 / (1 + expf(-o));               prune_op = op < min_opacity
+ *     big_self   = prune_world_size && smax > world_limit          (world_limit = 0.1f * extent, from the caller)
+ *     child_s[k] = logf(expf(s[k]) / 1.6f)
+ *     big_child  = prune_world_size && max_k expf(child_s[k]) > world_limit      (the same NaN-propagating max)
+ *     self kept          iff !split_sel && !prune_op && !big_self
+ *     a clone emitted    iff  clone_sel && !prune_op && !big_self
+ *     two children emitted iff split_sel && !prune_op && !big_child
+ * (upstream's screen-size test is absent on purpose: densification_postfix zeroes max_radii2D before the final prune
+ * reads it, so inside this sequence it never selects anything.)  The output rows are upstream's order, four segments,
+ * each ascending in i: kept selves | clones | first children | second children.  counts[4] (device int32) receives
+ * kept, clones, split parents whose children are emitted, N_out = kept + clones + 2 split; `workspace`
+ * (gsr_densify_workspace_bytes(N) bytes, 16-byte aligned) receives what gsr_densify_apply needs.  Three launches on
+ * `stream`, no allocation, no synchronisation.  N == 0 returns GSR_OK without touching the device (counts is not written).
+ * GSR_E_INVALID: struct_size, N < 0 or N > 2^30, a null pointer, a workspace that is too small or misaligned.
+ *
+ * gsr_densify_apply moves the data: ONE launch for up to GSR_ADAM_MAX_GROUPS groups.  Group k has sources param,
+ * exp_avg, exp_avg_sq (N, M) and destinations out_* (N_out, M), contiguous float32; the four moment pointers are all
+ * given or all NULL (a group that never stepped).  Output row r with parent i (r's segment decides its kind):
+ *     kept self:  param, exp_avg, exp_avg_sq of row i, bit for bit
+ *     clone:      param of row i bit for bit, zero moments
+ *     child c (0 first, 1 second): zero moments; param of row i bit for bit, except
+ *         role GSR_DENSIFY_SCALING:  child_s[k] above
+ *         role GSR_DENSIFY_XYZ:      ((R_k0 v0 + R_k1 v1) + R_k2 v2) + xyz[i][k],  v[j] = expf(s[j]) * noise[i][c][j]
+ * with R the rotation matrix of the raw quaternion q = rotation[4 i ..] = (r, x, y, z), as the 3DGS python layer's
+ * build_rotation forms it: n = sqrtf(((r r + x x) + y y) + z z), each component divided by n, then
+ *     R00 = 1 - 2 (y y + z z)   R01 = 2 (x y - r z)       R02 = 2 (x z + r y)
+ *     R10 = 2 (x y + r z)       R11 = 1 - 2 (x x + z z)   R12 = 2 (y z - r x)
+ *     R20 = 2 (x z - r y)       R21 = 2 (y z + r x)       R22 = 1 - 2 (x x + y y)
+ * `xyz`, `scaling`, `rotation` are the model's raw tensors (the XYZ / SCALING groups' params, as a rule); `noise` is
+ * (N, 2, 3) standard normals INDEXED BY PARENT, so it can be drawn before the number of splits is known.  `parent`
+ * (int32, N_out) always receives i for every row.  N and the workspace are those of the plan; N_out is what the caller
+ * read from counts[3] -- rows past the plan's own N_out are not written.  Pointers need only be 4-byte aligned: a group
+ * whose destinations are all 16-byte aligned is written in 16-byte vectors.  Gaussian indices are 32-bit, element
+ * indices 64-bit.  No allocation, no synchronisation.  N == 0 and N_out == 0 return GSR_OK without a launch.
+ * GSR_E_INVALID: struct_size, N outside 0..2^30, N_out outside 0..2 N, num_groups outside 0..GSR_ADAM_MAX_GROUPS, an M
+ * outside 1..4096 (the XYZ and SCALING roles: M = 3), an unknown role, a null pointer, moments given in part, a
+ * workspace too small or misaligned, an output that overlaps an input, the workspace or another output.
+ */
+#define GSR_DENSIFY_COPY 0
+#define GSR_DENSIFY_XYZ 1
+#define GSR_DENSIFY_SCALING 2
+typedef struct GsrDensifyPlan {
+    int32_t struct_size;         /* sizeof(GsrDensifyPlan): the library rejects a mismatch (GSR_E_INVALID) */
+    int32_t N;                   /* Gaussians */
+    const float *grad_accum;     /* (N) -- device, as are denom, scaling, opacity */
+    const float *denom;          /* (N) */
+    const float *scaling;        /* (N, 3) raw (log) */
+    const float *opacity;        /* (N) raw (logit) */
+    float grad_threshold;        /* [host] */
+    float min_opacity;           /* [host] */
+    float dense_limit;           /* [host] percent_dense * extent */
+    float world_limit;           /* [host] 0.1f * extent */
+    int32_t prune_world_size;    /* upstream's `if max_screen_size:` */
+    int32_t reserved;
+    int32_t *counts;             /* device int32[4]: kept, clones, split, N_out */
+    void *workspace;
+    int64_t workspace_bytes;
+} GsrDensifyPlan;
+typedef struct GsrDensifyGroup {
+    const float *param;          /* (N, M) */
+    const float *exp_avg;        /* (N, M) or NULL */
+    const float *exp_avg_sq;
+    float *out_param;            /* (N_out, M) */
+    float *out_exp_avg;          /* (N_out, M) or NULL */
+    float *out_exp_avg_sq;
+    int32_t M;                   /* floats per Gaussian, 1 <= M <= 4096 */
+    int32_t role;                /* GSR_DENSIFY_* */
+} GsrDensifyGroup;
+typedef struct GsrDensifyApply {
+    int32_t struct_size;         /* sizeof(GsrDensifyApply) */
+    int32_t N;                   /* the plan's N */
+    int32_t N_out;               /* counts[3], as the caller read it */
+    int32_t num_groups;
+    const void *workspace;       /* the plan's */
+    int64_t workspace_bytes;
+    const float *xyz;            /* (N, 3) */
+    const float *scaling;        /* (N, 3) raw */
+    const float *rotation;       /* (N, 4) raw */
+    const float *noise;          /* (N, 2, 3) */
+    int32_t *parent;             /* (N_out) */
+    GsrDensifyGroup groups[GSR_ADAM_MAX_GROUPS];
+} GsrDensifyApply;
+int64_t gsr_densify_workspace_bytes(int32_t N); /* [host] multiple of 256 */
+int gsr_densify_plan(const GsrDensifyPlan *plan, void *stream);
+int gsr_densify_apply(const GsrDensifyApply *apply, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
