@@ -300,6 +300,7 @@ def dense_view_camera(name: str = "xarm6_align", width: int = 640, height: int =
 
 
 def training_camera(width: int = 800, height: int = 800, fov_deg: float = 60.0) -> ViewParams:
+    """The IDENTITY view at the origin with a square field of view (what the benchmarks render), not a posed camera."""
     return identity_camera(width, height, fov_deg)
 
 

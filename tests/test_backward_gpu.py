@@ -1,7 +1,12 @@
 """GPU parity of the backward pass: gsr_backward vs the backward oracle, and the autograd
 path of the drop-in ``GaussianRasterizer``.  Tolerance: the CUDA / HIP kernels accumulate float atomics in an
 arbitrary order and use the hardware exp2, the oracle sums the same float terms in binary64: 99.9 % of the
-entries within 2e-3 relative (+1e-3 of the tensor's max as absolute floor), worst entry within 2e-2."""
+entries within 2e-3 relative (+1e-3 of the tensor's max as absolute floor), worst entry within 2e-2.
+
+Every case here looks through the identity view at the origin at packed, aligned (P,16,3) SH, into the wrapper's own
+gradient arena.  Rotated cameras with unequal fields of view, the other SH layouts and Gaussian counts (the three
+variants of sh_backward_kernel), the raw parameter space against the oracle, and NaN-filled caller-owned gradient
+buffers between guard floats: tests/test_backward_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch

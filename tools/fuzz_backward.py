@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Randomised gradient parity on the GPU: gsr_backward vs the backward oracle (tests/helpers_bwd.run_case tolerance)
-over random sizes, image shapes, SH degrees, antialiasing and splat scales.  Usage: fuzz_backward.py [iterations] [seed]."""
+over random sizes, image shapes, look-at cameras with unequal fields of view, SH layouts (1, 4, 9 or 16 coefficients) and
+degrees, antialiasing and splat scales.  Usage: fuzz_backward.py [iterations] [seed]."""
 import os
 import sys
 import time
@@ -21,7 +22,10 @@ def main():
     for it in range(iters):
         n = int(rng.choice([50, 700, 4000, 12000]))
         w, h = int(rng.integers(8, 200)), int(rng.integers(8, 150))
-        rep = hb.run_case(n, w, h, seed=int(rng.integers(1 << 30)), aa=bool(rng.random() < 0.3), deg=int(rng.integers(0, 4)),
+        M = int(rng.choice([1, 4, 9, 16]))
+        deg = int(rng.integers(0, {1: 0, 4: 1, 9: 2, 16: 3}[M] + 1))
+        rep = hb.run_case(n, w, h, seed=int(rng.integers(1 << 30)), aa=bool(rng.random() < 0.3), deg=deg, M=M,
+                          cam=hb.random_rotated_camera(rng, w, h),
                           bg=tuple(rng.random(3).tolist()), scale_boost=float(rng.uniform(-0.5, 1.5)),
                           with_invdepth=bool(rng.random() < 0.7))
         worst = max(worst, max(v["max_norm_err"] for v in rep.values()))
