@@ -753,6 +753,109 @@ int64_t gsr_densify_workspace_bytes(int32_t N); /* [host] multiple of 256 */
 int gsr_densify_plan(const GsrDensifyPlan *plan, void *stream);
 int gsr_densify_apply(const GsrDensifyApply *apply, void *stream);
 
+/*
+ * Nearest point of a reference cloud for every point of a query cloud (nnquery.hip), and the two real2sim steps that rest
+ * on it: label transfer with bounding-box validation (GSWorld real2sim_utils/segment_utils.py) and the sums of one
+ * point-to-point ICP iteration with scaling (real2sim/scripts/icp.py).  This comment is the definition.
+ *
+ * gsr_nn_build builds the search structure of `ref` (n_ref, 3) float32 once, into caller-owned `index_mem` of
+ * gsr_nn_index_bytes(n_ref) bytes (256-byte aligned): the points in Morton order (30-bit codes in the cloud's own bounds),
+ * their sorted codes, the permutation back to the caller's numbering and its inverse, the bounds, and the AABBs of boxes of
+ * 1024 consecutive sorted points.  `ref` is not needed afterwards.  Coordinates must be finite (not checked here).
+ * n_ref == 0 is legal and launches nothing.  No allocation, no synchronisation.
+ *
+ * gsr_nn_query: for every query i < n_query, with x' the query itself or, when use_transform, row r of it
+ *     x'[r] = fmaf(m[r][2], z, fmaf(m[r][1], y, m[r][0] * x)) + m[r][3]          (m = query_transform, row-major 3 x 4)
+ * and d2(j) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), d = x' - ref[j], all in binary32:
+ *     index[i] = the j that minimises d2(j), the LOWEST such j on ties;  dist2[i] = that d2
+ *     index[i] = -1, dist2[i] = +inf  when n_ref == 0, when a coordinate of x' is not finite, or when max_dist2 >= 0 and
+ *                                     the minimum exceeds it (d2 == max_dist2 is still a match)
+ * `query_out` (n_query, 3), when not NULL, receives x'.  The answer is exact -- it is the O(n m) definition whatever the
+ * launch shape or the order of the queries.  `workspace`: gsr_nn_query_workspace_bytes(n_query) bytes, 256-byte aligned.
+ * n_query == 0 returns GSR_OK without a launch.  No allocation, no synchronisation.
+ * GSR_E_INVALID: struct_size, a negative size, a null pointer that is needed, a NaN max_dist2, memory too small or misaligned.
+ */
+size_t gsr_nn_index_bytes(int32_t n_ref);            /* [host] multiple of 256, monotone in n_ref */
+int gsr_nn_build(int32_t n_ref, const float *ref, void *index_mem, size_t index_bytes, void *stream);
+typedef struct GsrNnQuery {
+    int32_t struct_size;         /* sizeof(GsrNnQuery) */
+    int32_t n_ref;               /* the n_ref index_mem was built for */
+    const void *index_mem;       /* what gsr_nn_build wrote (may be NULL when n_ref == 0) */
+    int64_t index_bytes;
+    int32_t n_query;
+    int32_t use_transform;       /* 0: query_transform is not read */
+    const float *query;          /* (n_query, 3) -- device */
+    float query_transform[12];   /* [host] row-major 3 x 4 */
+    float max_dist2;             /* [host] negative: no limit (-0 is the limit 0) */
+    int32_t reserved;
+    int32_t *index;              /* (n_query) out */
+    float *dist2;                /* (n_query) out */
+    float *query_out;            /* (n_query, 3) out, or NULL */
+    void *workspace;
+    int64_t workspace_bytes;
+} GsrNnQuery;
+size_t gsr_nn_query_workspace_bytes(int32_t n_query); /* [host] multiple of 256, monotone in n_query */
+int gsr_nn_query(const GsrNnQuery *query, void *stream);
+
+/*
+ * gsr_label_transfer restates transfer_labels_with_bbox's validation loop per point i < n, with p = points[i] (the
+ * query's query_out), j = index[i], and the box table's rows in the caller's order (row k: box_labels[k], box_bounds[k] =
+ * min xyz, max xyz).  The squared distance to a box is
+ *     e[c] = fmaxf(fmaxf(min[c] - p[c], 0), p[c] - max[c]);   b2 = fmaf(e2, e2, fmaf(e1, e1, e0 * e0))
+ * and t2 = threshold * threshold, both in binary32:
+ *     L = -1 when j < 0 or j >= n_ref, else ref_labels[j]
+ *     L == -1                         -> labels[i] = -1
+ *     no row carries L                -> labels[i] = -1
+ *     b2(first row that carries L) <= t2 -> labels[i] = L
+ *     otherwise                       -> the label of the row with the smallest b2 among rows with b2 <= t2 (strict <
+ *                                        in row order: the first row wins a tie), or -1 when no row qualifies
+ * One launch, one thread per point, the table in LDS.  n == 0 returns GSR_OK without a launch.
+ * GSR_E_INVALID: struct_size, n < 0, n_boxes outside 0..GSR_LABEL_MAX_BOXES, a null pointer that is needed.
+ */
+#define GSR_LABEL_MAX_BOXES 1024
+typedef struct GsrLabelTransfer {
+    int32_t struct_size;         /* sizeof(GsrLabelTransfer) */
+    int32_t n;
+    const int32_t *index;        /* (n) from gsr_nn_query */
+    const float *points;         /* (n, 3) the transformed queries */
+    const int32_t *ref_labels;   /* (n_ref) */
+    int32_t n_ref;
+    int32_t n_boxes;
+    const int32_t *box_labels;   /* (n_boxes) -- device */
+    const float *box_bounds;     /* (n_boxes, 6) -- device */
+    float threshold;             /* [host] */
+    int32_t reserved;
+    int32_t *labels;             /* (n) out */
+} GsrLabelTransfer;
+int gsr_label_transfer(const GsrLabelTransfer *transfer, void *stream);
+
+/*
+ * gsr_icp_moments: the sums one Umeyama update needs, in binary64, over the inliers i (0 <= index[i] < n_ref) of a
+ * query of the transformed sources: p' = the transform of source[i] as gsr_nn_query forms it (binary32, then widened),
+ * q = the reference point index[i] of the built structure.  sums[18] (device doubles):
+ *     [0] count   [1..3] sum p'   [4..6] sum q   [7..15] sum p'[r] q[c] at 7 + 3 r + c   [16] sum |p'|^2   [17] sum dist2[i]
+ * Per-workgroup partial sums in a fixed order, then one workgroup adds them in a fixed order: no floating atomics, two
+ * calls give the same bytes.  `workspace`: GSR_ICP_WORKSPACE_BYTES bytes, 8-byte aligned.  n == 0 or n_ref == 0 writes zeros.
+ * GSR_E_INVALID: struct_size, a negative size, a null pointer that is needed, a workspace too small or misaligned.
+ */
+#define GSR_ICP_WORKSPACE_BYTES (256 * 18 * 8)
+typedef struct GsrIcpMoments {
+    int32_t struct_size;         /* sizeof(GsrIcpMoments) */
+    int32_t n;                   /* source points */
+    const float *source;         /* (n, 3) */
+    float transform[12];         /* [host] row-major 3 x 4 */
+    int32_t use_transform;
+    int32_t n_ref;
+    const void *index_mem;       /* the structure the query ran against */
+    int64_t index_bytes;
+    const int32_t *index;        /* (n) */
+    const float *dist2;          /* (n) */
+    double *sums;                /* (18) out */
+    void *workspace;
+    int64_t workspace_bytes;
+} GsrIcpMoments;
+int gsr_icp_moments(const GsrIcpMoments *moments, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
