@@ -815,3 +815,31 @@ def densify_apply(N: int, N_out: int, workspace, xyz, scaling, rotation, noise, 
         s.groups[k] = _lib.GsrDensifyGroup(*(v or None for v in t[:6]), t[6], t[7])
     with torch.cuda.device(dev):
         check(lib().gsr_densify_apply(C.byref(s), _stream(dev)))
+
+
+# ---- the fused training loss (include/gsr.h gsr_train_loss / gsr_train_loss_backward) -----------------------------------
+def train_loss_scratch_floats(H: int, W: int) -> int:
+    return int(lib().gsr_train_loss_scratch_floats(int(H), int(W)))
+
+
+def train_loss_scratch_needed(H: int, W: int, exposure: bool, alpha_mask: bool) -> int:
+    """``gsr_train_loss_scratch_needed``: the floats of scratch a call of this size with / without an exposure and an alpha
+    mask needs (host arithmetic; at most ``train_loss_scratch_floats(H, W)``)."""
+    a = _lib.GsrTrainLoss(struct_size=C.sizeof(_lib.GsrTrainLoss), H=int(H), W=int(W), exposure=8 if exposure else None,
+                          alpha_mask=8 if alpha_mask else None)  # (presence only: nothing is dereferenced)
+    return int(lib().gsr_train_loss_scratch_needed(C.byref(a)))
+
+
+_TRAIN_LOSS_PTRS = frozenset((3, 4, 5, 6, 7, 8, 9, 12, 14, 15, 16, 17, 18, 19))  # positions of the pointers in `vals`
+
+
+def train_loss(vals, device, backward: bool = False, binding: str = "auto") -> None:
+    """One ``gsr_train_loss`` (or ``_backward``) on the current stream of ``device``.  ``vals``: the fields of ``GsrTrainLoss``
+    behind ``struct_size`` in the header's order, buffers as device addresses (0 = NULL); gsworld_amd/ssim.py has checked
+    dtype, device and layout.  No synchronisation."""
+    if _use_ext(binding, "train_loss"):
+        _ext.train_loss(device.index if device.index is not None else torch.cuda.current_device(), bool(backward), tuple(vals))
+        return
+    a = _lib.GsrTrainLoss(C.sizeof(_lib.GsrTrainLoss), *(v or None if k in _TRAIN_LOSS_PTRS else v for k, v in enumerate(vals)))
+    with torch.cuda.device(device):
+        check((lib().gsr_train_loss_backward if backward else lib().gsr_train_loss)(C.byref(a), _stream(device)))

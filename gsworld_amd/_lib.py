@@ -206,6 +206,16 @@ class GsrDensifyApply(C.Structure):
                 ("groups", GsrDensifyGroup * ADAM_MAX_GROUPS)]
 
 
+class GsrTrainLoss(C.Structure):
+    """The arguments of ``gsr_train_loss`` / ``gsr_train_loss_backward`` (include/gsr.h): the fused training loss."""
+    _fields_ = [("struct_size", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("lambda_dssim", C.c_float),
+                ("color", C.c_void_p), ("target", C.c_void_p), ("exposure", C.c_void_p), ("alpha_mask", C.c_void_p),
+                ("invdepth", C.c_void_p), ("mono_invdepth", C.c_void_p), ("depth_mask", C.c_void_p),
+                ("depth_weight", C.c_float), ("keep_for_backward", C.c_int32), ("scratch", C.c_void_p),
+                ("scratch_floats", C.c_int64), ("loss", C.c_void_p), ("terms", C.c_void_p), ("grad_loss", C.c_void_p),
+                ("dL_dcolor", C.c_void_p), ("dL_dinvdepth", C.c_void_p), ("dL_dexposure", C.c_void_p)]
+
+
 class GsrProfile(C.Structure):
     _fields_ = [("frames", C.c_int32), ("stage_ms", C.c_double * 5)]
 
@@ -292,6 +302,14 @@ def lib() -> C.CDLL:
     L.gsr_densify_plan.argtypes = [C.POINTER(GsrDensifyPlan), C.c_void_p]
     L.gsr_densify_apply.restype = C.c_int
     L.gsr_densify_apply.argtypes = [C.POINTER(GsrDensifyApply), C.c_void_p]
+    L.gsr_train_loss_scratch_floats.restype = C.c_size_t
+    L.gsr_train_loss_scratch_floats.argtypes = [C.c_int32, C.c_int32]
+    L.gsr_train_loss_scratch_needed.restype = C.c_size_t
+    L.gsr_train_loss_scratch_needed.argtypes = [C.POINTER(GsrTrainLoss)]
+    L.gsr_train_loss.restype = C.c_int
+    L.gsr_train_loss.argtypes = [C.POINTER(GsrTrainLoss), C.c_void_p]
+    L.gsr_train_loss_backward.restype = C.c_int
+    L.gsr_train_loss_backward.argtypes = [C.POINTER(GsrTrainLoss), C.c_void_p]
     L.gsr_profile_enable.restype = C.c_int
     L.gsr_profile_enable.argtypes = [C.c_int]
     L.gsr_profile_collect.restype = C.c_int

@@ -565,6 +565,13 @@ int gsr_launch_tile_place(const GsrSettings &st, int32_t P, const GeomState &g, 
                           const ImageState &img, bool debug, hipStream_t stream);
 int gsr_launch_rowscan(uint32_t *table, const uint32_t *n_ptr, int nb_stride, int chunk, int rows, uint32_t *totals,
                        bool debug, hipStream_t stream);
+// the ssim passes of gsr_photometric_loss (ssim.hip) for the training loss (train_loss.hip)
+size_t gsr_ssim_loss_blocks(int planes, int H, int W);
+int gsr_launch_ssim_loss_forward(int planes, int H, int W, const float *img, const float *target, int keep, int clamp01,
+                                 float *maps, float *partials, hipStream_t stream);
+int gsr_launch_ssim_loss_backward(int planes, int H, int W, const float *img, const float *target, const float *grad_loss,
+                                  const float *maps, float w_ssim, float w_l1, int clamp01, float *dL_dimg,
+                                  hipStream_t stream);
 int gsr_radix_passes(int bits, int bits_per_pass);
 int gsr_radix_sort_u32(uint32_t *key[2], uint32_t *val[2], const uint32_t *n_ptr, int64_t n_max, int bits,
                        int bits_per_pass, int start_side, uint32_t *table, uint32_t *totals, bool debug,

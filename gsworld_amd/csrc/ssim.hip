@@ -366,15 +366,10 @@ extern "C" int gsr_photometric_loss(int32_t planes, int32_t H, int32_t W, const 
     }
     hipStream_t stream = (hipStream_t)stream_;
     const size_t n = (size_t)planes * H * W;
-    const dim3 grid(gsr_div_up(W, kTX), gsr_div_up(H, kTY), planes);
-    const int nb = (int)(grid.x * grid.y * grid.z);
+    const int nb = (int)gsr_ssim_loss_blocks(planes, H, W);
     float *partials = scratch, *maps = scratch + 2 * (size_t)nb;  // (the pairs first: read as float2)
-    float *dm_dmu1 = maps, *dm_dsigma1_sq = maps + n, *dm_dsigma12 = maps + 2 * n;
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    const Gauss11 g = make_window();
-    hipLaunchKernelGGL(ssim_forward_kernel<true>, grid, dim3(GSR_BLOCK), 0, stream, H, W, C1, C2, g, img, target,
-                       keep_for_backward ? 1 : 0, (float *)nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, clamp01, partials);
-    if (int e = gsr_check_launch("photometric_loss (forward)", false, stream)) return e;
+    if (int e = gsr_launch_ssim_loss_forward(planes, H, W, img, target, keep_for_backward, clamp01, maps, partials, stream))
+        return e;
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kFinT), 0, stream, (const float *)partials, nb, (double)n,
                        lambda_dssim, loss);
     return gsr_check_launch("photometric_loss (sum)", false, stream);
@@ -391,15 +386,38 @@ extern "C" int gsr_photometric_loss_backward(int32_t planes, int32_t H, int32_t 
         gsr_set_error("gsr_photometric_loss_backward: null pointer");
         return GSR_E_INVALID;
     }
-    hipStream_t stream = (hipStream_t)stream_;
     const size_t n = (size_t)planes * H * W;
-    const dim3 grid(gsr_div_up(W, kTX), gsr_div_up(H, kTY), planes);
-    const size_t nb = (size_t)grid.x * grid.y * grid.z;
-    const float *maps = scratch + 2 * nb;
+    const float *maps = scratch + 2 * gsr_ssim_loss_blocks(planes, H, W);
     const float w_ssim = (float)(-(double)lambda_dssim / (double)n);
     const float w_l1 = (float)((1.0 - (double)lambda_dssim) / (double)n);
     // (LOSS mode: the dL_dmap slot carries the incoming gradient of the scalar loss, one float on the device, or NULL = 1)
+    return gsr_launch_ssim_loss_backward(planes, H, W, img, target, grad_loss, maps, w_ssim, w_l1, clamp01, dL_dimg,
+                                         (hipStream_t)stream_);
+}
+
+// ---- the two ssim passes in LOSS mode: gsr_photometric_loss above and the training loss (train_loss.hip) launch them here --
+size_t gsr_ssim_loss_blocks(int planes, int H, int W) {
+    return (size_t)gsr_div_up(W, kTX) * gsr_div_up(H, kTY) * planes;
+}
+
+// partials: 2 floats per workgroup (ssim sum, |.| sum); maps: 3 planes H W floats, written when `keep`
+int gsr_launch_ssim_loss_forward(int planes, int H, int W, const float *img, const float *target, int keep, int clamp01,
+                                 float *maps, float *partials, hipStream_t stream) {
+    const size_t n = (size_t)planes * H * W;
+    const dim3 grid(gsr_div_up(W, kTX), gsr_div_up(H, kTY), planes);
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    hipLaunchKernelGGL(ssim_forward_kernel<true>, grid, dim3(GSR_BLOCK), 0, stream, H, W, C1, C2, make_window(), img, target,
+                       keep ? 1 : 0, (float *)nullptr, maps, maps + n, maps + 2 * n, clamp01, partials);
+    return gsr_check_launch("ssim loss (forward)", false, stream);
+}
+
+// dL_dimg = grad_loss (w_ssim d sum ssim / d img + w_l1 sign(img - target)), through the clamp when `clamp01`
+int gsr_launch_ssim_loss_backward(int planes, int H, int W, const float *img, const float *target, const float *grad_loss,
+                                  const float *maps, float w_ssim, float w_l1, int clamp01, float *dL_dimg,
+                                  hipStream_t stream) {
+    const size_t n = (size_t)planes * H * W;
+    const dim3 grid(gsr_div_up(W, kTX), gsr_div_up(H, kTY), planes);
     hipLaunchKernelGGL(ssim_backward_kernel<true>, grid, dim3(GSR_BLOCK), 0, stream, H, W, make_window(), img, target,
                        grad_loss, maps, maps + n, maps + 2 * n, dL_dimg, w_ssim, w_l1, clamp01);
-    return gsr_check_launch("photometric_loss (gradient)", false, stream);
+    return gsr_check_launch("ssim loss (gradient)", false, stream);
 }

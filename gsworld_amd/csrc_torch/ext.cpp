@@ -765,6 +765,40 @@ void densify_apply(int64_t device_index, int64_t N, int64_t N_out, int64_t works
     TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
 }
 
+// ---- the fused training loss (gsworld_amd._C.train_loss) ------------------------------------------------------------------
+// `vals`: the fields of GsrTrainLoss behind struct_size in the header's order, buffers as device addresses (0 = NULL).
+void train_loss(int64_t device_index, bool backward, const py::tuple &vals) {
+    TORCH_CHECK(vals.size() == 20, "train_loss: 20 values expected, got ", vals.size());
+    auto F = [&](size_t k) { return reinterpret_cast<float *>((uintptr_t)vals[k].cast<int64_t>()); };
+    GsrTrainLoss s;
+    std::memset(&s, 0, sizeof(s));
+    s.struct_size = (int32_t)sizeof(GsrTrainLoss);
+    s.H = vals[0].cast<int32_t>();
+    s.W = vals[1].cast<int32_t>();
+    s.lambda_dssim = (float)vals[2].cast<double>();
+    s.color = F(3);
+    s.target = F(4);
+    s.exposure = F(5);
+    s.alpha_mask = F(6);
+    s.invdepth = F(7);
+    s.mono_invdepth = F(8);
+    s.depth_mask = F(9);
+    s.depth_weight = (float)vals[10].cast<double>();
+    s.keep_for_backward = vals[11].cast<int32_t>();
+    s.scratch = F(12);
+    s.scratch_floats = vals[13].cast<int64_t>();
+    s.loss = F(14);
+    s.terms = F(15);
+    s.grad_loss = F(16);
+    s.dL_dcolor = F(17);
+    s.dL_dinvdepth = F(18);
+    s.dL_dexposure = F(19);
+    const torch::Device dev(torch::kCUDA, (c10::DeviceIndex)device_index);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int rc = backward ? gsr_train_loss_backward(&s, current_stream(dev)) : gsr_train_loss(&s, current_stream(dev));
+    TORCH_CHECK(rc == GSR_OK, "libgsr_hip error ", rc, ": ", gsr_last_error());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -814,5 +848,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("densification_stats", &densification_stats);
     m.def("densify_plan", &densify_plan);
     m.def("densify_apply", &densify_apply);
+    m.def("train_loss", &train_loss);
     m.def("version", []() { return std::string(gsr_version()); });
 }

@@ -32,7 +32,9 @@ def _stock_getters(pc) -> bool:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, separate_sh=False,
-           override_color=None, use_trained_exp=False):
+           override_color=None, use_trained_exp=False, raw_color=False):
+    # raw_color: "render" is the rasterizer's colour as it is -- no exposure, no clamp -- for a loss that applies both
+    # itself (gsworld_amd.ssim.training_loss); the default is upstream's result
     # gradient carrier for the 2D means (densification statistics read its .grad); the no-grad shortcut below creates it
     # only when somebody reads it from the result
     def make_screenspace_points():
@@ -96,7 +98,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             means3D=means3D, means2D=means2D, opacities=pc._opacity, shs=pc._features_dc.contiguous(),
             shs_rest=pc._features_rest.contiguous(), scales=pc._scaling, rotations=pc._rotation,
             param_space=RAW_OPACITY | RAW_SCALES | RAW_ROTATIONS)
-        return _finish(rendered_image, radii, depth_image, screenspace_points, viewpoint_camera, pc, use_trained_exp)
+        return _finish(rendered_image, radii, depth_image, screenspace_points, viewpoint_camera, pc, use_trained_exp,
+                       raw_color=raw_color)
 
     scales = rotations = cov3D_precomp = None
     if fused:
@@ -147,7 +150,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
                 if not renderer.bounded:  # (a list sized by P x tiles cannot overflow: nothing to read back)
                     renderer.ensure_valid(enqueue)
         return _finish(rendered_image, radii, depth_image, make_screenspace_points, viewpoint_camera, pc,
-                       use_trained_exp, lazy=True)
+                       use_trained_exp, lazy=True, raw_color=raw_color)
 
     shs = colors_precomp = None
     if override_color is None:
@@ -168,7 +171,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     rendered_image, radii, depth_image = rasterizer(
         means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity, scales=scales,
         rotations=rotations, cov3D_precomp=cov3D_precomp)
-    return _finish(rendered_image, radii, depth_image, screenspace_points, viewpoint_camera, pc, use_trained_exp)
+    return _finish(rendered_image, radii, depth_image, screenspace_points, viewpoint_camera, pc, use_trained_exp,
+                   raw_color=raw_color)
 
 
 class _View:
@@ -226,13 +230,15 @@ class _LazyResult(dict):
     del _n, _materialised
 
 
-def _finish(rendered_image, radii, depth_image, screenspace_points, viewpoint_camera, pc, use_trained_exp, lazy=False):
-    if use_trained_exp:
+def _finish(rendered_image, radii, depth_image, screenspace_points, viewpoint_camera, pc, use_trained_exp, lazy=False,
+            raw_color=False):
+    if use_trained_exp and not raw_color:
         exposure = pc.get_exposure_from_name(viewpoint_camera.image_name)
         rendered_image = torch.matmul(rendered_image.permute(1, 2, 0), exposure[:3, :3]).permute(2, 0, 1) + \
             exposure[:3, 3, None, None]
 
-    rendered_image = rendered_image.clamp(0, 1)
+    if not raw_color:
+        rendered_image = rendered_image.clamp(0, 1)
     if lazy:  # (`screenspace_points` is then the function that makes them)
         return _LazyResult({"render": rendered_image, "radii": radii, "depth": depth_image},
                            {"viewspace_points": screenspace_points,

@@ -36,11 +36,48 @@ class Camera(nn.Module):
         self._image = image
         self._resolution = resolution
         self.alpha_mask = None
+        if len(getattr(image, "getbands", tuple)()) == 4:  # a fourth channel masks the loss (None = all ones)
+            from utils.general_utils import PILtoTorch
+
+            rgba = PILtoTorch(image, resolution)
+            self.alpha_mask = rgba[3:4].to(self.data_device)
+            self._image = rgba[:3].clamp(0.0, 1.0).to(self.data_device)
+        if train_test_exp and is_test_view:
+            # upstream's split of a held-out view under train_test_exp: its exposure is fitted on the LEFT half (the copy of
+            # the view in the training list has its right half masked out), and it is scored on the RIGHT half (the copy in
+            # the test list has its left half masked out)
+            if self.alpha_mask is None:
+                self.alpha_mask = torch.ones((1, self.image_height, self.image_width), dtype=torch.float32,
+                                             device=self.data_device)
+            if is_test_dataset:
+                self.alpha_mask[..., :self.image_width // 2] = 0
+            else:
+                self.alpha_mask[..., self.image_width // 2:] = 0
         self.invdepthmap = None
+        self.depth_mask = None
         self.depth_reliable = False
         if invdepthmap is not None:
-            self.invdepthmap = torch.as_tensor(np.asarray(invdepthmap), dtype=torch.float32)[None].to(self.data_device)
-            self.depth_reliable = depth_params is not None
+            # upstream's handling of a monocular inverse-depth map, resized with PIL (bilinear) where it uses cv2
+            from PIL import Image as _Image
+
+            inv = np.asarray(invdepthmap, dtype=np.float32)
+            if inv.ndim != 2:
+                inv = inv[..., 0]
+            if (inv.shape[1], inv.shape[0]) != (self.image_width, self.image_height):
+                inv = np.asarray(_Image.fromarray(inv).resize((self.image_width, self.image_height), _Image.BILINEAR),
+                                 dtype=np.float32)  # (a float32 array makes a mode "F" image)
+            inv = np.where(inv < 0, np.float32(0), inv)
+            mask = np.ones_like(inv)
+            self.depth_reliable = True
+            if depth_params is not None:
+                if (depth_params["scale"] < 0.2 * depth_params["med_scale"]
+                        or depth_params["scale"] > 5 * depth_params["med_scale"]):
+                    self.depth_reliable = False
+                    mask = mask * 0
+                if depth_params["scale"] > 0:
+                    inv = inv * np.float32(depth_params["scale"]) + np.float32(depth_params["offset"])
+            self.invdepthmap = torch.from_numpy(np.ascontiguousarray(inv))[None].to(self.data_device)
+            self.depth_mask = torch.from_numpy(mask)[None].to(self.data_device)
         self.zfar = ZFAR
         self.znear = ZNEAR
         self.trans = trans

@@ -163,6 +163,35 @@ class GaussianModel:
             self.optimizer = SparseGaussianAdam(groups, lr=0.0, eps=1e-15)
         else:
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        # the schedules and the exposure optimizer of upstream's training_setup: built for an args object that carries the
+        # exposure_lr_* fields (OptimizationParams); one set up the old way keeps the constant rates above and has neither
+        self.exposure_optimizer = None
+        self.xyz_scheduler_args = self.exposure_scheduler_args = None
+        if hasattr(training_args, "exposure_lr_init"):
+            from utils.general_utils import get_expon_lr_func
+
+            if getattr(self, "_exposure", None) is not None:
+                self.exposure_optimizer = torch.optim.Adam([self._exposure])
+            self.xyz_scheduler_args = get_expon_lr_func(
+                lr_init=training_args.position_lr_init * self.spatial_lr_scale,
+                lr_final=training_args.position_lr_final * self.spatial_lr_scale,
+                lr_delay_mult=training_args.position_lr_delay_mult, max_steps=training_args.position_lr_max_steps)
+            self.exposure_scheduler_args = get_expon_lr_func(
+                training_args.exposure_lr_init, training_args.exposure_lr_final,
+                lr_delay_steps=training_args.exposure_lr_delay_steps, lr_delay_mult=training_args.exposure_lr_delay_mult,
+                max_steps=training_args.iterations)
+
+    def update_learning_rate(self, iteration):
+        """Learning rates of this iteration: the exposure optimizer's and the xyz group's; -> the xyz rate."""
+        if self.xyz_scheduler_args is None:
+            raise RuntimeError("update_learning_rate: training_setup was given no schedule (args without exposure_lr_*)")
+        if self.exposure_optimizer is not None and self.pretrained_exposures is None:
+            for group in self.exposure_optimizer.param_groups:
+                group["lr"] = self.exposure_scheduler_args(iteration)
+        for group in self.optimizer.param_groups:
+            if group["name"] == "xyz":
+                group["lr"] = lr = self.xyz_scheduler_args(iteration)
+                return lr
 
     def add_densification_stats(self, viewspace_point_tensor, update_filter):
         """upstream's bookkeeping of an iteration.  ``update_filter`` = the int32 ``radii`` of the frame: one fused launch
@@ -368,3 +397,16 @@ class GaussianModel:
         # (frozen tensors, (N,1,1) opacity, semantics) -- that flavour is read_gaussian_ply's default.
         read_gaussian_ply(path, self, upstream=True)
         self.active_sh_degree = self.max_sh_degree
+        if use_train_test_exp:  # the exposures `Scene.save` left in the model path, two folders above the PLY
+            import json
+
+            exposure_file = os.path.join(os.path.dirname(path), os.pardir, os.pardir, "exposure.json")
+            if os.path.exists(exposure_file):
+                with open(exposure_file) as f:
+                    exposures = json.load(f)
+                self.pretrained_exposures = {name: torch.tensor(e, dtype=torch.float32, device=self._xyz.device)
+                                             for name, e in exposures.items()}
+                print("Pretrained exposures loaded.")
+            else:
+                print(f"No exposure to be loaded at {exposure_file}")
+                self.pretrained_exposures = None

@@ -28,3 +28,48 @@ def PILtoTorch(pil_image, resolution):
     resized = pil_image.resize(resolution)
     img = torch.from_numpy(np.array(resized)) / 255.0
     return img.permute(2, 0, 1) if img.dim() == 3 else img.unsqueeze(-1).permute(2, 0, 1)
+
+
+def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
+    """Upstream's schedule: log-linear from ``lr_init`` (step 0) to ``lr_final`` (step ``max_steps``), optionally eased in
+    over the first ``lr_delay_steps`` steps from ``lr_delay_mult`` times the value; 0 before step 0 and when both ends are 0."""
+    import numpy as np
+
+    def helper(step):
+        if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+            return 0.0
+        if lr_delay_steps > 0:
+            delay_rate = lr_delay_mult + (1 - lr_delay_mult) * np.sin(0.5 * np.pi * np.clip(step / lr_delay_steps, 0, 1))
+        else:
+            delay_rate = 1.0
+        t = np.clip(step / max_steps, 0, 1)
+        return delay_rate * np.exp(np.log(lr_init) * (1 - t) + np.log(lr_final) * t)
+
+    return helper
+
+
+def safe_state(silent):
+    """Seeds python, numpy and torch with 0; with ``silent`` the training script's prints are dropped (upstream stamps
+    them with the time instead: not reproduced)."""
+    import random
+    import sys
+
+    import numpy as np
+
+    if silent:
+        class _Quiet:
+            def __init__(self, out):
+                self._out = out
+
+            def write(self, s):
+                pass
+
+            def flush(self):
+                self._out.flush()
+
+        sys.stdout = _Quiet(sys.stdout)
+    random.seed(0)
+    np.random.seed(0)
+    torch.manual_seed(0)
+    if torch.cuda.is_available():
+        torch.cuda.set_device(torch.device("cuda:0"))

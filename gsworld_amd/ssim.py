@@ -150,3 +150,96 @@ def photometric_loss(img, target, lambda_dssim: float = 0.2, clamp01: bool = Fal
     elementwise / reduction launches: the value is summed in a fixed order; the backward pass writes the gradient
     w.r.t. ``img`` (through the clamp), already scaled by the incoming gradient.  An extension: ``fused_ssim`` stays the drop-in."""
     return _PhotometricLoss.apply(img, target, lambda_dssim, clamp01)
+
+
+def _loss_plane(t, what, shape, dev):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"training_loss: {what} must live on a HIP device (no CPU path)")
+    if t.device != dev:
+        raise RuntimeError(f"training_loss: {what} is on {t.device}, color on {dev}")
+    t = t.detach()
+    if t.ndim < 2 or tuple(t.shape[-2:]) != tuple(shape[1:]) or t.numel() != shape[0] * shape[1] * shape[2]:
+        raise RuntimeError(f"training_loss: {what} has shape {tuple(t.shape)}, {tuple(shape)} expected")
+    return t.to(torch.float32).contiguous()
+
+
+class _TrainingLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, target, exposure, alpha_mask, invdepth, mono_invdepth, depth_mask, lambda_dssim, depth_weight):
+        from . import _C
+        if not isinstance(color, torch.Tensor) or not color.is_cuda:
+            raise RuntimeError("training_loss: color must live on a HIP device (no CPU path)")
+        if color.ndim != 3 or color.shape[0] != 3 or color.shape[1] < 1 or color.shape[2] < 1:
+            raise RuntimeError(f"training_loss: color must be (3, H, W), got {tuple(color.shape)}")
+        dev = color.device
+        H, W = int(color.shape[1]), int(color.shape[2])
+        c = _loss_plane(color, "color", (3, H, W), dev)
+        t = _loss_plane(target, "target", (3, H, W), dev)
+        if t is None:
+            raise RuntimeError("training_loss: target is missing")
+        depth = (invdepth is not None, mono_invdepth is not None, depth_mask is not None)
+        if any(depth) and not all(depth):
+            raise RuntimeError("training_loss: invdepth, mono_invdepth and depth_mask come together or not at all")
+        e = exposure
+        if e is not None:
+            if not isinstance(e, torch.Tensor) or not e.is_cuda or e.numel() != 12 or tuple(e.shape[-2:]) != (3, 4):
+                raise RuntimeError("training_loss: exposure must be a (3, 4) tensor on a HIP device")
+            e = e.detach().to(torch.float32).contiguous()
+        a = _loss_plane(alpha_mask, "alpha_mask", (1, H, W), dev)
+        d, m, k = (_loss_plane(v, n, (1, H, W), dev) for v, n in
+                   ((invdepth, "invdepth"), (mono_invdepth, "mono_invdepth"), (depth_mask, "depth_mask")))
+        need_grad = any(ctx.needs_input_grad[i] for i in (0, 2, 4))
+        scratch = torch.empty(_C.train_loss_scratch_needed(H, W, e is not None, a is not None), dtype=torch.float32,
+                              device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty(4, dtype=torch.float32, device=dev)
+        scalars = (H, W, float(lambda_dssim), float(depth_weight), int(need_grad))
+        _C.train_loss(_loss_vals(scalars, (c, t, e, a, d, m, k), scratch, (loss, terms, None, None, None, None)), dev)
+        if need_grad:
+            ctx.save_for_backward(c, t, e, a, d, m, k, scratch)
+            ctx.scalars = scalars
+            ctx.dtypes = (color.dtype, exposure.dtype if exposure is not None else None,
+                          invdepth.dtype if invdepth is not None else None)
+            ctx.shapes = (exposure.shape if exposure is not None else None, invdepth.shape if invdepth is not None else None)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        from . import _C
+        # (the addresses are those of the tensors as they come back now: saved-tensor hooks may have moved them)
+        c, t, e, a, d, m, k, scratch = ctx.saved_tensors
+        g = g.detach().to(device=c.device, dtype=torch.float32).contiguous()
+        dcolor = torch.empty_like(c)
+        dinv = torch.empty_like(d) if d is not None else None
+        dexp = torch.empty(12, dtype=torch.float32, device=c.device) if e is not None else None
+        _C.train_loss(_loss_vals(ctx.scalars, (c, t, e, a, d, m, k), scratch, (None, None, g, dcolor, dinv, dexp)), c.device,
+                      backward=True)
+        dt_c, dt_e, dt_d = ctx.dtypes
+        sh_e, sh_d = ctx.shapes
+        return (dcolor.to(dt_c), None, dexp.view(sh_e).to(dt_e) if dexp is not None else None, None,
+                dinv.view(sh_d).to(dt_d) if dinv is not None else None, None, None, None, None)
+
+
+def _loss_vals(scalars, inputs, scratch, outputs):
+    """The fields of ``GsrTrainLoss`` behind ``struct_size`` in the header's order (``_C.train_loss``), addresses taken now."""
+    H, W, lam, depth_weight, keep = scalars
+    ptr = lambda v: v.data_ptr() if v is not None else 0  # noqa: E731
+    return [H, W, lam, *(ptr(v) for v in inputs), depth_weight, keep, ptr(scratch), scratch.numel(),
+            *(ptr(v) for v in outputs)]
+
+
+def training_loss(color, target, lambda_dssim: float = 0.2, exposure=None, alpha_mask=None, invdepth=None,
+                  mono_invdepth=None, depth_mask=None, depth_weight: float = 0.0):
+    """The loss of a 3DGS training iteration as ONE autograd node (``gsr_train_loss`` + ``_backward``, include/gsr.h holds
+    the definition): ``x = clamp(color E, 0, 1) * alpha_mask``, ``(1 - lambda) l1(x, target) + lambda (1 - ssim(x, target))``
+    and, with the depth group, ``+ depth_weight * mean|(invdepth - mono_invdepth) * depth_mask|``.  ``color`` (3, H, W) is the
+    rasterizer's colour before exposure and clamp, ``exposure`` (3, 4) upstream's per-image affine.  Gradients reach
+    ``color``, ``exposure`` and ``invdepth``.  -> a 0-d tensor whose ``.terms`` is a device tensor (total, L1, mean ssim,
+    unweighted depth L1): nothing is read back to the host."""
+    loss, terms = _TrainingLoss.apply(color, target, exposure, alpha_mask, invdepth, mono_invdepth, depth_mask,
+                                      lambda_dssim, depth_weight)
+    loss.terms = terms
+    return loss

@@ -856,6 +856,58 @@ typedef struct GsrIcpMoments {
 } GsrIcpMoments;
 int gsr_icp_moments(const GsrIcpMoments *moments, void *stream);
 
+/*
+ * gsr_train_loss / gsr_train_loss_backward: the whole loss of a 3DGS training iteration (upstream train.py with
+ * train_test_exp, an alpha mask and the inverse-depth regularisation) and its gradients, three launches each way.
+ * All device arrays are float32.  With E = exposure (row-major 3 x 4), per pixel and in this order of operations:
+ *     y_c = ((color_0 E[0][c] + color_1 E[1][c]) + color_2 E[2][c]) + E[c][3]      (exposure == NULL: y = color)
+ *     x_c = clamp(y_c, 0, 1)   (a NaN stays a NaN);    alpha_mask != NULL: x_c = x_c * alpha
+ *     loss = (1 - lambda) mean|x - target| + lambda (1 - mean ssim(x, target))      (the sums of gsr_photometric_loss)
+ *     depth group present: loss += depth_weight * mean over H W of |(invdepth - mono_invdepth) * depth_mask|
+ * Every sum over pixels is per-workgroup partial sums in a fixed order (binary32), then one workgroup adds them in a fixed
+ * order in binary64: no floating atomics, two calls give the same bits.  Without exposure, alpha mask and depth group the
+ * value and dL_dcolor are those of gsr_photometric_loss(clamp01 = 1), bit for bit.
+ * terms (4 floats, or NULL): total, mean|x - target|, mean ssim, the unweighted depth mean (0 without the group).
+ * gsr_train_loss_backward -- after a gsr_train_loss with keep_for_backward != 0 on the same scratch and the same inputs --
+ * writes, all scaled by grad_loss (one float on the device, NULL = 1):
+ *     dL_dcolor (3,H,W);  dL_dinvdepth (H,W) when the depth group is present;  dL_dexposure (12) when exposure is.
+ * sign(0) = 0; the clamp passes the gradient where 0 <= y <= 1 (bounds included) and stops it outside, towards color and
+ * towards E alike.  dL_dexposure[4 i + c] = sum color_i g_c (i, c < 3), dL_dexposure[4 c + 3] = sum g_c, g = dL/dy.
+ * scratch: 8-byte aligned; gsr_train_loss_scratch_floats(H, W) floats suffice for every call of that size (0 for an invalid
+ * size), gsr_train_loss_scratch_needed(loss) is what THIS call needs -- the same arithmetic on the host, from H, W and which of
+ * exposure / alpha_mask are present (without both, a third less) -- and what scratch_floats is checked against; forward and
+ * backward of one call agree on it.
+ * GSR_E_INVALID (before any device work): struct_size, H or W < 1 or H W > 2^28, a null color / target / scratch / loss,
+ * a depth group of which only a part is present, a non-finite lambda_dssim or depth_weight, scratch_floats too small,
+ * a scratch that is not 8-byte aligned, and in the backward a missing dL_dcolor, dL_dinvdepth (depth group) or dL_dexposure (exposure).
+ */
+typedef struct GsrTrainLoss {
+    int32_t struct_size;         /* sizeof(GsrTrainLoss) */
+    int32_t H, W;
+    float lambda_dssim;          /* [host] */
+    const float *color;          /* (3,H,W) the rasterizer's out_color, before exposure and clamp */
+    const float *target;         /* (3,H,W) */
+    const float *exposure;       /* (12) or NULL */
+    const float *alpha_mask;     /* (H,W) or NULL */
+    const float *invdepth;       /* (H,W) the rasterizer's out_invdepth -- depth group: all three or none */
+    const float *mono_invdepth;  /* (H,W) */
+    const float *depth_mask;     /* (H,W) */
+    float depth_weight;          /* [host] */
+    int32_t keep_for_backward;
+    float *scratch;
+    int64_t scratch_floats;
+    float *loss;                 /* (1) out */
+    float *terms;                /* (4) out, or NULL */
+    const float *grad_loss;      /* backward: (1) or NULL = 1 */
+    float *dL_dcolor;            /* backward: (3,H,W) out */
+    float *dL_dinvdepth;         /* backward: (H,W) out (depth group) */
+    float *dL_dexposure;         /* backward: (12) out (exposure) */
+} GsrTrainLoss;
+size_t gsr_train_loss_scratch_floats(int32_t H, int32_t W);
+size_t gsr_train_loss_scratch_needed(const GsrTrainLoss *loss);
+int gsr_train_loss(const GsrTrainLoss *loss, void *stream);
+int gsr_train_loss_backward(const GsrTrainLoss *loss, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
